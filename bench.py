@@ -12,8 +12,14 @@ Workload = BASELINE.json configs[1] ("AVQA eval, Llama-2-7B + BEATs + CLIP-ViT-L
 metric is quoted on (10 s clip, 8 frames, 256 output tokens, 128-token prompt).  Weights are seeded N(0,0.02)
 (no checkpoints offline), inputs synthetic and already resident in HBM when the timed region starts.
 
+A plain run does what the headline needs and no more: set-up, W warm-up steps, K timed steps, the outputs of the last timed step
+when --dump-outputs DIR is given, and the JSON line.  Everything else it can measure (roofline figures, the other workloads and
+operating points, the CPU baseline) runs only with --full, behind the timed steps.
+
 The JSON line carries
   value        : clips / wall time of the K timed steps on the SHIPPED path (native sequencers, HIP-graph decode, no profiler attached);
+  ms_per_step  : wall time of one timed step (the K steps between barriers / K).
+With --full it also carries
   roofline     : the dominant kernel by time.  At the default batch this is the decode attention
                  kernel (HBM-bound: every live K/V row of every clip is read once per generated token): algorithmic
                  KV bytes of the sampled launches / their HIP-event time, against the 8 TB/s HBM3E peak.  Sampling: ONE extra,
@@ -34,15 +40,15 @@ import os
 import sys
 import time
 
+T_PROCESS0 = time.perf_counter()   # the ONE JSON line is printed last: everything optional behind the headline is admitted against --time-budget
+                                   # (seconds of this process, the torch import included), so that a launcher's time limit never costs the line itself
+
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")      # dmabuf IPC: RCCL across processes fails without it on this driver
 
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-
-T_PROCESS0 = time.perf_counter()   # the ONE JSON line is printed last: everything optional behind the headline is admitted against --time-budget
-                                   # (seconds of this process), so that a launcher's time limit never costs the line itself
 
 
 def time_left(args) -> float:
@@ -544,6 +550,28 @@ def avss_pixel_path(model, um, args):
                    "mask decoder's bf16 tolerance (tests/test_model_gpu.py)"}
 
 
+DUMP_BYTES = 64_000_000          # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(out_dir, res):
+    """--dump-outputs: what the last timed step handed its caller on rank 0, as float32 .npy files: `sequences` = the generated ids of every
+    clip [clips, new_tokens] in clip order (ids < 2^24 are exact in float32) and `first_logits` = the fp32 first-step logits [clips, V].  Where
+    the logits of all clips would pass DUMP_BYTES, a fixed seeded sample of whole rows is written, and `first_logits_clip_ids` names its clips."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    cid, ids, logits = res
+    seq = ids.cpu().numpy().astype(np.float32)
+    np.save(os.path.join(out_dir, "sequences.npy"), seq)
+    if logits is None:                                    # --no-gather-logits
+        return
+    lg = logits.float().cpu().numpy()
+    n, V = lg.shape
+    k = max(0, min(n, (DUMP_BYTES - seq.nbytes - 4 * n - 3 * 4096) // (4 * V)))      # room beside the ids, the clip ids and three .npy headers
+    rows = np.arange(n) if k == n else np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+    np.save(os.path.join(out_dir, "first_logits.npy"), np.ascontiguousarray(lg[rows]))
+    np.save(os.path.join(out_dir, "first_logits_clip_ids.npy"), cid.cpu().numpy()[rows].astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -558,18 +586,25 @@ def main():
     ap.add_argument("--decode-streams", type=int, default=int(os.environ.get("CRAB_DECODE_STREAMS", "1")),
                     help="decode groups replayed on separate HIP streams (KV-cache attention of one overlaps projections of another)")
     ap.add_argument("--llm", default="llama")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline does not need: one instrumented step for the roofline blocks and "
+                         "(N = 1) the pixel path, the Qwen2 variant, the reference's operating points and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the ids and first-step logits of the last timed step to DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-gather-logits", action="store_true", help="gather token ids only (default: ids + first-step fp32 logits of every clip)")
     ap.add_argument("--strong", action="store_true",
                     help="strong scaling: --clips is the TOTAL over all ranks (contiguous blocks, the first total %% N ranks hold one more clip); "
                          "default is weak scaling (--clips per GPU)")
-    ap.add_argument("--time-budget", type=float, default=float(os.environ.get("CRAB_BENCH_TIME_BUDGET", "760")),
-                    help="seconds this process may take in all (N = 1): the reference operating points and the Qwen2 variant behind the headline are admitted "
-                         "against it in order of importance and say so when skipped - the JSON line is printed last and must not be lost to a launcher's limit "
-                         "(the driver runs --steps 20 --warmup 5: 27 steps of 16.6 s before anything optional)")
+    ap.add_argument("--time-budget", type=float, default=float(os.environ.get("CRAB_BENCH_TIME_BUDGET", "540")),
+                    help="with --full: seconds this process may take in all (N = 1); the pixel path, the Qwen2 variant and the reference operating points "
+                         "behind the headline are admitted against it in order of importance and say so when skipped - the JSON line is printed last and "
+                         "must not be lost to a launcher's limit (540 s: a --full run ends within 10 minutes unless its own steps take longer)")
     ap.add_argument("--no-operating-points", action="store_true",
-                    help="skip the extra (untimed-region) runs at the reference's own operating points: eval batch 8, 10 frames, 2-s audio windows")
+                    help="with --full: skip the extra (untimed-region) runs at the reference's own operating points: eval batch 8, 10 frames, 2-s audio windows")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks here, exactly as the driver's
@@ -690,6 +725,8 @@ def main():
         if i == 0:
             torch.cuda.synchronize()
             print(f"[bench rank {rank}/{world}] first warm-up step {time.perf_counter() - tw:.1f} s", file=sys.stderr, flush=True)
+        else:
+            print(f"[bench rank {rank}/{world}] warm-up step {i + 1}/{args.warmup} {time.perf_counter() - tw:.1f} s", file=sys.stderr, flush=True)
     torch.cuda.synchronize()
     t_warm = time.perf_counter() - t_w
     # capacity: generate() splits a batch whose KV cache + scratch do not fit the device into groups that run one after the other (with a
@@ -700,10 +737,9 @@ def main():
                  "kv_bytes_per_clip": int(plan.get("bytes_per_seq", 0)), "free_gib_before": round(free0 / 2 ** 30, 1), "free_gib_after_warmup": round(free1 / 2 ** 30, 1)}
     # ---- the timed region: the SHIPPED path (native layer sequencers, every decode step a HIP-graph replay, no profiler attached)
     assert ops.PROFILER is None
-    # the LAST timed step carries the three phase marks of generate() (encode_begin / prefill_end / decode_end: three HIP event records on a
-    # ~16 s step, nothing else changes - the native sequencers and the graph replays run underneath): the source of prefill_roofline.  r01-r05
-    # spent one extra un-timed step on them; its 17 s now go to the blocks behind the headline (the driver's run has a time limit)
-    phase_prof = ops.KernelProfiler(phase_only=True)
+    # with --full the LAST timed step carries the three phase marks of generate() (encode_begin / prefill_end / decode_end: three HIP event records
+    # on a ~16 s step, nothing else changes - the native sequencers and the graph replays run underneath): the source of prefill_roofline
+    phase_prof = ops.KernelProfiler(phase_only=True) if args.full else None
     sync()
     t0 = time.perf_counter()
     step_ms = []
@@ -714,20 +750,25 @@ def main():
         res = step()                       # generate() ends with a device->host read of the step count: the step is complete
         ops.PROFILER = None
         step_ms.append(round((time.perf_counter() - ts) * 1e3, 1))
+        # one stderr line per ~16 s step (microseconds): a long run is never silent for minutes before its JSON line
+        print(f"[bench rank {rank}/{world}] timed step {i_step + 1}/{args.steps} {step_ms[-1] / 1e3:.1f} s", file=sys.stderr, flush=True)
     sync()
     dt = time.perf_counter() - t0
-    pre_ms, dec_ms = phase_prof.phase_ms()
-    # ---- ONE extra, un-timed, instrumented step for the roofline blocks: HIP events around every GEMM >= 512 rows (per-launch Python
-    # sequence instead of the native sequencer) and around the decode-attention kernel on every 32nd decode step, which runs eagerly
-    # (bit-identical to the graph replay it stands in for, tests/test_model_gpu.py).  Its wall time is reported next to the timed one.
-    prof = ops.KernelProfiler(min_m=512, decode_every=32)
-    ops.PROFILER = prof
-    sync()
-    ti = time.perf_counter()
-    step()
-    sync()
-    instrumented_ms = (time.perf_counter() - ti) * 1e3
-    ops.PROFILER = None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
+    if args.full:
+        pre_ms, dec_ms = phase_prof.phase_ms()
+        # ---- ONE extra, un-timed, instrumented step for the roofline blocks: HIP events around every GEMM >= 512 rows (per-launch Python
+        # sequence instead of the native sequencer) and around the decode-attention kernel on every 32nd decode step, which runs eagerly
+        # (bit-identical to the graph replay it stands in for, tests/test_model_gpu.py).  Its wall time is reported next to the timed one.
+        prof = ops.KernelProfiler(min_m=512, decode_every=32)
+        ops.PROFILER = prof
+        sync()
+        ti = time.perf_counter()
+        step()
+        sync()
+        instrumented_ms = (time.perf_counter() - ti) * 1e3
+        ops.PROFILER = None
     rank_ms = [round(dt / args.steps * 1e3, 2)]
     rank_infos = [rank_info]
     if dist is not None:
@@ -740,7 +781,6 @@ def main():
         rank_ms = [round(float(t.item()) / args.steps * 1e3, 2) for t in allt]
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-    psum = prof.summary()
 
     if rank == 0:
         # the gather really delivered every rank's clips (ordered by clip id) to rank 0
@@ -748,47 +788,6 @@ def main():
         assert args.no_gather_logits or (res[2] is not None and tuple(res[2].shape) == (n_total, V)), "first-step logits not gathered"
         n_clips = n_total * args.steps
         S = 126 + 32 * args.frames + 320
-        # per-kernel roofline entries from the live HIP-event samples; the dominant kernel is the one with the largest
-        # (estimated) total time in the timed region: GEMM buckets are timed on every launch, the decode-attention
-        # kernel on the sampled eager decode steps (x its launch count = steps * (new_tokens-1) * layers)
-        n_layers = um.config.num_hidden_layers
-        entries = []
-        for name, d in psum.items():
-            avg_ms = d["ms"] / d["launches"]
-            if name.startswith("attn_decode"):
-                total_launches = args.steps * (args.new_tokens - 1) * n_layers       # launches in the TIMED region; the average comes from the instrumented step
-                ach = d["work"] / (d["ms"] * 1e-3) / 1e9
-                e = {"bound": "hbm", "kernel": name, "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(ach / HBM_PEAK_GBS, 4),
-                     "traffic": round(d["work"] / d["launches"] * ATTN_DECODE_TRAFFIC_PER_ALGO_BYTE),
-                     "algorithmic_bytes_per_launch": round(d["work"] / d["launches"]),
-                     "traffic_source": "PMC ratio from profiles/r06_pmc_attn_decode.txt (= r05_pmc_attn_decode_512clips.txt; separate --pmc passes at 512 clips x ctx 830) x this run's bytes"}
-            else:
-                total_launches = d["launches"] * args.steps                            # the instrumented step's launches x the K timed steps
-                ach = d["work"] / (d["ms"] * 1e-3) / 1e12
-                e = {"bound": "mfma", "kernel": name, "achieved": round(ach, 1), "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                     "frac": round(ach / MFMA_PEAK_TFLOPS, 4), "traffic": None,
-                     "note": "all launches of this kernel in the instrumented step: decoder prefill projections AND the encoders' (CLIP K = 1024) shapes",
-                     "by_class": {c: {"launches": v["launches"], "achieved": round(v["work"] / (v["ms"] * 1e-3) / 1e12, 1),
-                                      "frac": round(v["work"] / (v["ms"] * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS, 4)}
-                                  for c, v in d.get("classes", {}).items() if v["ms"] > 0}}
-            e.update({"sampled_launches": d["launches"], "avg_launch_us": round(avg_ms * 1e3, 1),
-                      "est_total_ms_in_timed_region": round(avg_ms * total_launches, 1)})
-            entries.append(e)
-        entries.sort(key=lambda e: -e["est_total_ms_in_timed_region"])
-        roof = entries[0] if entries else None
-        roof_mfma = next((e for e in entries if e["bound"] == "mfma"), None)
-        # the north-star target quantity: fused encoder + decoder prefill (prepare_multimodal_inputs + chunked prefill +
-        # first-token selection) of all clips, algorithmic FLOPs / HIP-event time of that phase
-        pre_ms_instr, _ = prof.phase_ms()
-        pre_flops = flops_per_clip(args.frames, 10, 48, S, V, um.config) * B                    # the ONE instrumented step
-        prefill_roof = {"bound": "mfma", "phase": "encoders + decoder prefill (whole phase, all kernels)",
-                        "achieved": round(pre_flops / (pre_ms * 1e-3) / 1e12, 1), "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                        "frac": round(pre_flops / (pre_ms * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS, 4),
-                        "ms_per_clip": round(pre_ms / B, 3), "decode_ms_per_clip": round(dec_ms / B, 3),
-                        "executed": _executed_block(pre_flops / B, S, um.config, pre_ms / B),
-                        "source": "the last timed step of the shipped path, which carries three phase marks (HIP event records); the per-launch instrumented step "
-                                  f"measures {round(pre_ms_instr / B, 3)} ms per clip for the same phase"}
         line = {
             "metric": "clips/sec prefill+decode (AVQA 10s clip, 8 frames, 256 out tok)",
             "value": round(n_clips / dt, 4), "unit": "clips/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -810,43 +809,85 @@ def main():
             "ranks": rank_infos,
             "prefill_tflop_per_clip": round(flops_per_clip(args.frames, 10, 48, S, V, um.config) / 1e12, 3),
             "step_ms": step_ms,
-            "timed_region": "the shipped path: native layer sequencers + HIP-graph replay of every decode step; no profiler attached except three phase-mark event records in the last step",
-            "instrumented_step": {"ms": round(instrumented_ms, 1), "timed": False,
-                                  "note": "one extra step after the timed region with HIP events on every GEMM >= 512 rows and on the decode attention of "
-                                          "every 32nd (eager) decode step: the source of roofline / roofline_mfma / prefill_roofline"},
+            "timed_region": "the shipped path: native layer sequencers + HIP-graph replay of every decode step; no profiler attached"
+                            + (" except three phase-mark event records in the last step" if args.full else ""),
             "residual_stream": "fp32" if ops.RESIDUAL_FP32 else "bf16",
-            "prefill_roofline": prefill_roof,
-            "roofline": roof,
-            "roofline_mfma": roof_mfma,
         }
-        # ---- behind the headline, in order of importance (every block admitted against --time-budget; the line is printed last):
-        #      BASELINE configs[4] (pixel path), configs[2] (Qwen2 on the AVE workload), the reference's own operating points, the CPU sample
-        if world == 1 and not args.no_operating_points and args.llm == "llama":
-            if time_left(args) < 25 + QWEN_RESERVE_S + CPU_RESERVE_S:
-                line["avss_pixel_path"] = {"skipped": f"--time-budget {args.time_budget:.0f} s: {max(time_left(args), 0):.0f} s left; `python scripts/bench_avs.py` gives it on its own"}
-            else:
+        if args.full:
+            # per-kernel roofline entries from the live HIP-event samples; the dominant kernel is the one with the largest
+            # (estimated) total time in the timed region: GEMM buckets are timed on every launch, the decode-attention
+            # kernel on the sampled eager decode steps (x its launch count = steps * (new_tokens-1) * layers)
+            n_layers = um.config.num_hidden_layers
+            entries = []
+            for name, d in prof.summary().items():
+                avg_ms = d["ms"] / d["launches"]
+                if name.startswith("attn_decode"):
+                    total_launches = args.steps * (args.new_tokens - 1) * n_layers       # launches in the TIMED region; the average comes from the instrumented step
+                    ach = d["work"] / (d["ms"] * 1e-3) / 1e9
+                    e = {"bound": "hbm", "kernel": name, "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": round(ach / HBM_PEAK_GBS, 4),
+                         "traffic": round(d["work"] / d["launches"] * ATTN_DECODE_TRAFFIC_PER_ALGO_BYTE),
+                         "algorithmic_bytes_per_launch": round(d["work"] / d["launches"]),
+                         "traffic_source": "PMC ratio from profiles/r06_pmc_attn_decode.txt (= r05_pmc_attn_decode_512clips.txt; separate --pmc passes at 512 clips x ctx 830) x this run's bytes"}
+                else:
+                    total_launches = d["launches"] * args.steps                            # the instrumented step's launches x the K timed steps
+                    ach = d["work"] / (d["ms"] * 1e-3) / 1e12
+                    e = {"bound": "mfma", "kernel": name, "achieved": round(ach, 1), "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                         "frac": round(ach / MFMA_PEAK_TFLOPS, 4), "traffic": None,
+                         "note": "all launches of this kernel in the instrumented step: decoder prefill projections AND the encoders' (CLIP K = 1024) shapes",
+                         "by_class": {c: {"launches": v["launches"], "achieved": round(v["work"] / (v["ms"] * 1e-3) / 1e12, 1),
+                                          "frac": round(v["work"] / (v["ms"] * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS, 4)}
+                                      for c, v in d.get("classes", {}).items() if v["ms"] > 0}}
+                e.update({"sampled_launches": d["launches"], "avg_launch_us": round(avg_ms * 1e3, 1),
+                          "est_total_ms_in_timed_region": round(avg_ms * total_launches, 1)})
+                entries.append(e)
+            entries.sort(key=lambda e: -e["est_total_ms_in_timed_region"])
+            # the north-star target quantity: fused encoder + decoder prefill (prepare_multimodal_inputs + chunked prefill +
+            # first-token selection) of all clips, algorithmic FLOPs / HIP-event time of that phase
+            pre_ms_instr, _ = prof.phase_ms()
+            pre_flops = flops_per_clip(args.frames, 10, 48, S, V, um.config) * B                    # the ONE instrumented step
+            line.update({
+                "instrumented_step": {"ms": round(instrumented_ms, 1), "timed": False,
+                                      "note": "one extra step after the timed region with HIP events on every GEMM >= 512 rows and on the decode attention of "
+                                              "every 32nd (eager) decode step: the source of roofline / roofline_mfma / prefill_roofline"},
+                "prefill_roofline": {"bound": "mfma", "phase": "encoders + decoder prefill (whole phase, all kernels)",
+                                     "achieved": round(pre_flops / (pre_ms * 1e-3) / 1e12, 1), "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                                     "frac": round(pre_flops / (pre_ms * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS, 4),
+                                     "ms_per_clip": round(pre_ms / B, 3), "decode_ms_per_clip": round(dec_ms / B, 3),
+                                     "executed": _executed_block(pre_flops / B, S, um.config, pre_ms / B),
+                                     "source": "the last timed step of the shipped path, which carries three phase marks (HIP event records); the per-launch "
+                                               f"instrumented step measures {round(pre_ms_instr / B, 3)} ms per clip for the same phase"},
+                "roofline": entries[0] if entries else None,
+                "roofline_mfma": next((e for e in entries if e["bound"] == "mfma"), None),
+            })
+            # ---- behind the headline, in order of importance (every block admitted against --time-budget; the line is printed last):
+            #      BASELINE configs[4] (pixel path), configs[2] (Qwen2 on the AVE workload), the reference's own operating points, the CPU sample
+            if world == 1 and not args.no_operating_points and args.llm == "llama":
+                if time_left(args) < 25 + QWEN_RESERVE_S + CPU_RESERVE_S:
+                    line["avss_pixel_path"] = {"skipped": f"--time-budget {args.time_budget:.0f} s: {max(time_left(args), 0):.0f} s left; `python scripts/bench_avs.py` gives it on its own"}
+                else:
+                    try:
+                        um._engine.invalidate()                # the headline's 2 x 100 GiB of KV cache: the pixel batch allocates its own (small) one
+                        torch.cuda.empty_cache()
+                        line["avss_pixel_path"] = avss_pixel_path(model, um, args)
+                    except Exception as e:      # the headline must still be reported
+                        line["avss_pixel_path"] = {"error": f"{type(e).__name__}: {e}"}
+                if time_left(args) < QWEN_RESERVE_S + CPU_RESERVE_S:
+                    line["qwen2_7b_variant"] = {"skipped": f"--time-budget {args.time_budget:.0f} s: {max(time_left(args), 0):.0f} s left; `python bench.py --llm qwen` gives the "
+                                                           "decoder as a line of its own"}
+                else:
+                    try:
+                        line["qwen2_7b_variant"] = qwen_variant(model, args)
+                    except Exception as e:      # the headline must still be reported
+                        line["qwen2_7b_variant"] = {"error": f"{type(e).__name__}: {e}"}
+                line["reference_operating_points"] = operating_points(model, um, args, eos, dt / args.steps)
+            line["process_s"] = {"time_budget": args.time_budget, "before_cpu_baseline": round(time.perf_counter() - T_PROCESS0, 1)}
+            if world == 1 and not args.no_cpu_baseline:
                 try:
-                    um._engine.invalidate()                # the headline's 2 x 100 GiB of KV cache: the pixel batch allocates its own (small) one
-                    torch.cuda.empty_cache()
-                    line["avss_pixel_path"] = avss_pixel_path(model, um, args)
-                except Exception as e:      # the headline must still be reported
-                    line["avss_pixel_path"] = {"error": f"{type(e).__name__}: {e}"}
-            if time_left(args) < QWEN_RESERVE_S + CPU_RESERVE_S:
-                line["qwen2_7b_variant"] = {"skipped": f"--time-budget {args.time_budget:.0f} s: {max(time_left(args), 0):.0f} s left; `python bench.py --llm qwen` gives the "
-                                                       "decoder as a line of its own"}
-            else:
-                try:
-                    line["qwen2_7b_variant"] = qwen_variant(model, args)
-                except Exception as e:      # the headline must still be reported
-                    line["qwen2_7b_variant"] = {"error": f"{type(e).__name__}: {e}"}
-            line["reference_operating_points"] = operating_points(model, um, args, eos, dt / args.steps)
-        line["process_s"] = {"time_budget": args.time_budget, "before_cpu_baseline": round(time.perf_counter() - T_PROCESS0, 1)}
-        if world == 1 and not args.no_cpu_baseline:
-            try:
-                line["cpu_baseline"] = cpu_baseline(args)
-            except Exception as e:      # the GPU number must still be reported
-                line["cpu_baseline"] = {"value": None, "unit": "clips/s", "cores": torch.get_num_threads(), "kind": "port",
-                                        "sample": f"failed: {type(e).__name__}: {e}"}
+                    line["cpu_baseline"] = cpu_baseline(args)
+                except Exception as e:      # the GPU number must still be reported
+                    line["cpu_baseline"] = {"value": None, "unit": "clips/s", "cores": torch.get_num_threads(), "kind": "port",
+                                            "sample": f"failed: {type(e).__name__}: {e}"}
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.barrier()
