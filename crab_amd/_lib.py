@@ -125,6 +125,7 @@ class LlamaIO(C.Structure):
         ("row_off", C.c_void_p),
         ("pos_ids", C.c_void_p), ("ld_pos", C.c_int64), ("kv_start", C.c_void_p),
         ("last_rows_only", C.c_int32),
+        ("kv_fp8", C.c_int32), ("k_scale", C.c_void_p), ("v_scale", C.c_void_p), ("scale_layer_stride", C.c_int64),
     ]
 
 
@@ -178,6 +179,8 @@ SYMBOLS = {
     "crab_qkv_rope_split": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "crab_qkv_rope_split_ids": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i64]),
     "crab_qkv_rope_split_ragged": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "crab_kv_quant_fp8": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _i64, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "crab_attn_decode_fp8": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp, _f, _vp]),
     "crab_attn_decode_masked": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp, _f, _vp]),
     "crab_attn_decode_keymask": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp, _f, _vp, _i64]),
     "crab_attn_fwd": (_i, [_vp, _vp, C.POINTER(AttnDesc)]),

@@ -129,10 +129,14 @@ int check_io(crab_ctx* ctx, const crab_llama_layer* L, const crab_llama_io* io, 
         if (io->pos0 + io->S > io->Tmax) return crab_fail(ctx, CRAB_E_INVALID, "llama_layer_prefill: rows do not fit the KV cache");
         if (io->row_off) return crab_fail(ctx, CRAB_E_INVALID, "llama_layer_prefill: row_off is a decode field (a prefill into a right-aligned cache advances k_cache / v_cache instead)");
         if (io->pos_ids && io->ld_pos < io->S) return crab_fail(ctx, CRAB_E_INVALID, "llama_layer_prefill: ld_pos < S");
+        if (io->kv_fp8)
+            return crab_fail(ctx, CRAB_E_INVALID, "llama_layer_prefill: kv_fp8 is a decode field (prefill into a bf16 block, then crab_kv_quant_fp8 moves it into the fp8 cache)");
     } else {
         if (io->S != 1) return crab_fail(ctx, CRAB_E_INVALID, "llama_layer_decode: one row per sequence (S == 1)");
         if (io->pos_ids || io->kv_start) return crab_fail(ctx, CRAB_E_INVALID, "llama_layer_decode: pos_ids / kv_start are prefill fields (a ragged decode step takes row_off)");
         if (!io->pos_dev && io->pos0 >= io->Tmax) return crab_fail(ctx, CRAB_E_INVALID, "llama_layer_decode: position outside the KV cache");
+        if (io->kv_fp8 && (io->kv_fp8 != 1 || !io->k_scale || !io->v_scale || (L->d != 64 && L->d != 128)))
+            return crab_fail(ctx, CRAB_E_INVALID, "llama_layer_decode: kv_fp8 = 1 needs k_scale / v_scale and head_dim 64 or 128");
     }
     return CRAB_OK;
 }
@@ -144,16 +148,19 @@ int run_layer(crab_ctx* ctx, void* stream, const crab_llama_layer* L, crab_llama
     uint16_t* vc = (uint16_t*)io->v_cache + (int64_t)layer_index * io->cache_layer_stride;
     const float scale = (float)(1.0 / sqrt((double)d));   // double, then rounded once: what crab_amd/decoder.py passes
     int rc;
+    // the FP8 KV cache (decode only, check_io): byte-strided codes + fp32 row scales; the projection leaves its raw row and
+    // crab_attn_decode_fp8 rotates, quantises, appends and attends
+    const bool fp8 = !prefill && io->kv_fp8;
     // ---- q|k|v
     // small batch (B * H blocks cannot fill 256 CUs): the projection leaves its raw row and ONE launch does RoPE + KV append + attention with
     // the context split over several blocks per head (crab_attn_decode_rope) - same choice as crab_amd/decoder.py
     // (a ragged batch - io->row_off - takes the general pair: projection with the per-row rotary offset, then the attention with a first visible key per row)
-    const bool fuse_attn = !prefill && !io->row_off && io->attn_ws && (long)B * H < CRAB_ATTN_SPLIT_BELOW && (d == 64 || d == 128) && (io->ldqkv & 7) == 0 &&
+    const bool fuse_attn = !prefill && !fp8 && !io->row_off && io->attn_ws && (long)B * H < CRAB_ATTN_SPLIT_BELOW && (d == 64 || d == 128) && (io->ldqkv & 7) == 0 &&
                            io->attn_ws_bytes >= crab_attn_decode_rope_workspace(B, H, d);
     GroupCall q{};
     q.x = io->h; q.ldx = io->ldh; q.out = io->qkv; q.ldc = io->ldqkv; q.act = CRAB_ACT_NONE;
     q.u_ready = (io->u_qkv_ready && L->qkv.RA) ? io->u2 : nullptr;
-    q.rope = !prefill && !fuse_attn;
+    q.rope = !prefill && !fuse_attn && !fp8;
     int fused_rope = 0;
     if (prefill) { q.rope_prefill_S = S; q.fused_prefill_rope = &fused_rope; }
     if ((rc = run_group(ctx, stream, &L->qkv, io, L, M, q, kc, vc))) return rc;
@@ -212,6 +219,13 @@ int run_layer(crab_ctx* ctx, void* stream, const crab_llama_layer* L, crab_llama
         a.B = B; a.H = H; a.Hk = Hk; a.Sq = S; a.Skv = io->pos0 + S; a.head_dim = d; a.causal = 1; a.scale = scale;
         a.kv_start = io->kv_start;                                  // left-pad mask (NULL: every key visible)
         if ((rc = crab_attn_fwd(ctx, stream, &a))) return rc;
+    } else if (fp8) {
+        uint8_t* kc8 = (uint8_t*)io->k_cache + (int64_t)layer_index * io->cache_layer_stride;
+        uint8_t* vc8 = (uint8_t*)io->v_cache + (int64_t)layer_index * io->cache_layer_stride;
+        if ((rc = crab_attn_decode_fp8(ctx, stream, io->qkv, io->ldqkv, io->rope_tab, kc8, vc8, io->k_scale + (int64_t)layer_index * io->scale_layer_stride,
+                                       io->v_scale + (int64_t)layer_index * io->scale_layer_stride, io->att, io->ldatt, B, H, Hk, d, io->Tmax, io->pos0,
+                                       io->pos_dev, scale, io->row_off)))
+            return rc;
     } else if (fuse_attn) {
         if ((rc = crab_attn_decode_rope(ctx, stream, io->qkv, io->ldqkv, io->rope_tab, kc, vc, io->att, io->ldatt, B, H, Hk, d, io->Tmax, io->pos0,
                                         io->pos_dev, scale, io->attn_ws, io->attn_ws_bytes)))

@@ -31,6 +31,7 @@ BF16 = torch.bfloat16
 import os as _os
 LAST_ROWS_ONLY = _os.environ.get("CRAB_PREFILL_LAST_ROWS", "1") != "0"
 RAGGED_PAD_MAX = 0.06     # a coalesced wave whose batches differ in length is prefilled as ONE padded batch while the padding costs at most this fraction of the prefill rows
+KV_CACHE_DTYPES = ("bf16", "fp8_e4m3")     # GenerationEngine(kv_cache_dtype=...): the default bf16 cache | the opt-in FP8 (OCP e4m3fn) cache with fp32 row scales
 NATIVE_LAYERS = True      # False: issue every launch of a layer from Python (A/B runs and the sequencer-equivalence tests)
 
 
@@ -154,8 +155,13 @@ class _Workspace:
 class GenerationEngine:
     """Prefill + greedy decode over a DecoderModel + lm_head.  Owns KV caches / workspaces (torch allocator)."""
 
-    def __init__(self, model: DecoderModel, lm_head: LMHead):
+    def __init__(self, model: DecoderModel, lm_head: LMHead, kv_cache_dtype: str = "bf16"):
+        """kv_cache_dtype: "bf16" (default) or "fp8_e4m3" - the opt-in FP8 KV cache of generate() / generate_many() (include/crab_hip.h "FP8 KV
+        cache": e4m3fn codes + one fp32 scale per cached row and KV head; prefill runs in bf16 into a staging block that crab_kv_quant_fp8 moves
+        over, decode attends the fp8 rows through crab_attn_decode_fp8).  Also settable per call: generate(..., kv_cache_dtype=...)."""
         self.model, self.lm_head = model, lm_head
+        self._stage = None             # fp8 mode: the bf16 staging pair a prefill chunk runs into (flat, grow-only)
+        self.kv_cache_dtype = kv_cache_dtype
         self.cfg = model.config
         self._rope = None
         self._ws = {}
@@ -170,7 +176,56 @@ class GenerationEngine:
     def device(self):
         return self.lm_head.weight.device
 
+    @staticmethod
+    def check_kv_cache_dtype(v) -> str:
+        if v not in KV_CACHE_DTYPES:
+            raise ValueError(f"kv_cache_dtype must be one of {' / '.join(repr(k) for k in KV_CACHE_DTYPES)}, got {v!r}")
+        return v
+
+    @property
+    def kv_cache_dtype(self) -> str:
+        """The mode of the call in progress (a per-call kv_cache_dtype argument overrides the engine's own for that call), else the engine's."""
+        return self._kv_mode
+
+    @kv_cache_dtype.setter
+    def kv_cache_dtype(self, v):
+        self._kv_mode = self.check_kv_cache_dtype(v)
+
+    @property
+    def _fp8(self) -> bool:
+        return getattr(self, "_kv_mode", "bf16") == "fp8_e4m3"
+
+    def _with_kv_mode(self, kv_cache_dtype, fn, *a, **k):
+        """Run fn under the per-call mode (None: whatever holds - the engine's, or the enclosing call's for the calls generate() makes itself)."""
+        if kv_cache_dtype is None:
+            return fn(*a, **k)
+        saved, self._kv_mode = self._kv_mode, self.check_kv_cache_dtype(kv_cache_dtype)
+        try:
+            return fn(*a, **k)
+        finally:
+            self._kv_mode = saved
+
+    def _staging(self, n: int, S: int):
+        """fp8 mode: the bf16 block [L, n, Hk, round_up(S, 64), d] x 2 one prefill chunk runs into before crab_kv_quant_fp8 moves it into the
+        fp8 cache - views of ONE persistent pair per engine, sized by the largest chunk seen."""
+        c = self.cfg
+        shape = (c.num_hidden_layers, n, c.num_key_value_heads, _round_up(S, 64), c.head_dim)
+        need = math.prod(shape)
+        if self._stage is None or self._stage[0].numel() < need or self._stage[0].device != self.device:
+            self._stage = None
+            self._stage = (torch.empty((need,), device=self.device, dtype=BF16), torch.empty((need,), device=self.device, dtype=BF16))
+        return self._stage[0][:need].view(shape), self._stage[1][:need].view(shape)
+
+    def staging_bytes(self, B: int, S: int) -> int:
+        """Bytes of the staging pair a generate() of B sequences of S rows needs in fp8 mode (0 in bf16 mode)."""
+        if not self._fp8:
+            return 0
+        c = self.cfg
+        n = min(B, max(1, 32768 // max(S, 1)))
+        return 2 * c.num_hidden_layers * n * c.num_key_value_heads * _round_up(S, 64) * c.head_dim * 2
+
     def invalidate(self):
+        self._stage = None
         self._dec = {}
         self._ws = {}
         self._kv = {}
@@ -271,12 +326,18 @@ class GenerationEngine:
         decode workspace / logits / output ids, its share of the prefill V^T scratch."""
         c = self.cfg
         Tmax = _round_up(S + max_new_tokens, 64)
-        kv = 2 * c.num_hidden_layers * c.num_key_value_heads * Tmax * c.head_dim * 2
+        kv = self.kv_bytes_per_sequence(Tmax)
         D, I = c.hidden_size, c.intermediate_size
         H, Hk, d = c.num_attention_heads, c.num_key_value_heads, c.head_dim
         xb = 2 if ops.RESIDUAL_FP32 else 0                    # the fp32 residual row costs 2 more bytes per element
         dec_row = (2 * D + (H + 2 * Hk) * d + H * d + I + 3 * 128) * 2 + D * xb + self.lm_head.weight.shape[0] * 4 + D * 2 + max_new_tokens * 8 + 64
         return kv + dec_row
+
+    def kv_bytes_per_sequence(self, Tmax: int) -> int:
+        """KV-cache bytes of one sequence: 2 L Hk Tmax d bf16, or in fp8 mode 2 L Hk Tmax (d + 4) (one byte per element + one fp32 scale per row)."""
+        c = self.cfg
+        rows = 2 * c.num_hidden_layers * c.num_key_value_heads * Tmax
+        return rows * (c.head_dim + 4) if self._fp8 else rows * c.head_dim * 2
 
     def fixed_bytes(self, B: int, S: int) -> int:
         """Batch-size independent scratch of a generate(): the prefill activation set of the largest chunk (<= 32768 rows) + its V^T."""
@@ -287,7 +348,10 @@ class GenerationEngine:
         per_row = (2 * D + (H + 2 * Hk) * d + H * d + I + 3 * 128) * 2 + Hk * d * 2 + (D * 2 if ops.RESIDUAL_FP32 else 0)
         have = self._ws.get("prefill")
         have_bytes = have.M * per_row if have is not None else 0
-        return max(rows * per_row - have_bytes, 0) + (256 << 20)                   # + split-K / router workspaces, allocator slack
+        stage = 0
+        if self._fp8:                                          # the bf16 staging pair of the fp8 mode's prefill (grow-only, like the prefill workspace)
+            stage = max(self.staging_bytes(B, S) - (2 * self._stage[0].numel() * 2 if self._stage is not None else 0), 0)
+        return max(rows * per_row - have_bytes, 0) + stage + (256 << 20)           # + split-K / router workspaces, allocator slack
 
     def _drop_stale_slots(self, keep_slots: int):
         """Free the persistent KV buffers, decode states (+ graphs) and decode workspaces of the slots >= keep_slots: what an earlier
@@ -316,7 +380,7 @@ class GenerationEngine:
         self._live_slots = max(1, int(slots))                  # what alloc_cache may NOT evict during the call being planned
         free, _total = torch.cuda.mem_get_info(self.device)
         cached = torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)
-        own = sum(kcb.numel() * 2 + vcb.numel() * 2 for (kcb, vcb) in self._kv.values())
+        own = sum(t.numel() * t.element_size() for bufs in self._kv.values() for t in bufs)
         return int(free + cached + own)
 
     def _evict_for(self, need_bytes: int, slot: int, slack: int = 4 << 30) -> bool:
@@ -350,25 +414,35 @@ class GenerationEngine:
         return groups
 
     def alloc_cache(self, B: int, Tmax: int, slot: Optional[int] = None):
-        """KV cache [L, B, Hk, Tmax, d] x 2.  slot = None: fresh zero-filled tensors (callers that keep the cache, e.g.
+        """KV cache [L, B, Hk, Tmax, d] x 2; in fp8 mode (kv_cache_dtype = "fp8_e4m3") FOUR tensors: uint8 codes x 2 and fp32 row scales
+        [L, B, Hk, Tmax] x 2.  slot = None: fresh zero-filled tensors (callers that keep the cache, e.g.
         forward(use_cache=True)).  slot = g: the engine's persistent buffers for decode group g, reused by every generate()
         of the same shape - rows at or beyond the live context are never read, so they need no clearing, and a 2 x 65 GB
         re-allocation per call (allocator splitting / hipFree retries: the second generate() of a process measured ~0.9 s
         slow) is avoided."""
         c = self.cfg
         shape = (c.num_hidden_layers, B, c.num_key_value_heads, Tmax, c.head_dim)
+        fp8 = self._fp8
         if slot is None:
+            if fp8:
+                return (torch.zeros(shape, device=self.device, dtype=torch.uint8), torch.zeros(shape, device=self.device, dtype=torch.uint8),
+                        torch.ones(shape[:4], device=self.device, dtype=torch.float32), torch.ones(shape[:4], device=self.device, dtype=torch.float32))
             return torch.zeros(shape, device=self.device, dtype=BF16), torch.zeros(shape, device=self.device, dtype=BF16)
         key = (slot,)
         hit = self._kv.get(key)
-        if hit is None or hit[0].shape != shape or hit[0].device != self.device:
+        if hit is None or hit[0].shape != shape or hit[0].device != self.device or (len(hit) == 4) != fp8:
             self._kv.pop(key, None)                  # drop the old buffers before allocating the new shape ...
             hit = None
             if self._dec.pop(slot, None) is not None:    # ... and the decode state (+ graph) that still references them: at
                 torch.cuda.empty_cache()                 # 256 clips the old and new caches (2 x ~65 GB each) do not fit together
             if self.device.type == "cuda":
-                self._evict_for(2 * 2 * math.prod(shape), slot)
-            self._kv[key] = (torch.empty(shape, device=self.device, dtype=BF16), torch.empty(shape, device=self.device, dtype=BF16))
+                self._evict_for(B * self.kv_bytes_per_sequence(Tmax), slot)
+            if fp8:
+                # fp8 mode: (k codes, v codes, k scales, v scales) - uint8 [L, B, Hk, Tmax, d] and fp32 [L, B, Hk, Tmax]
+                self._kv[key] = (torch.empty(shape, device=self.device, dtype=torch.uint8), torch.empty(shape, device=self.device, dtype=torch.uint8),
+                                 torch.empty(shape[:4], device=self.device, dtype=torch.float32), torch.empty(shape[:4], device=self.device, dtype=torch.float32))
+            else:
+                self._kv[key] = (torch.empty(shape, device=self.device, dtype=BF16), torch.empty(shape, device=self.device, dtype=BF16))
         return self._kv[key]
 
     # ------------------------------------------------------------------ the layer table of the native sequencer
@@ -405,7 +479,8 @@ class GenerationEngine:
 
     def _layers_native(self, ws: _Workspace, B: int, S: int, kc: torch.Tensor, vc: torch.Tensor, b0: int, Tmax: int, pos0: int,
                        pos_dev: Optional[torch.Tensor], vt: Optional[torch.Tensor], t0: int = 0, row_off: Optional[torch.Tensor] = None,
-                       pos_ids: Optional[torch.Tensor] = None, kv_start: Optional[torch.Tensor] = None, last_rows: bool = False):
+                       pos_ids: Optional[torch.Tensor] = None, kv_start: Optional[torch.Tensor] = None, last_rows: bool = False,
+                       kv_scales=None):
         """The whole stack through ONE C call (crab_llama_layers, csrc/llama_layer.hip): the same launches in the same order as the
         per-launch Python sequence below, which is kept for the runs that time individual kernels (ops.PROFILER)."""
         io = _lib.LlamaIO()
@@ -430,13 +505,16 @@ class GenerationEngine:
         io.B, io.S, io.Tmax, io.pos0, io.u_qkv_ready = B, S, Tmax, pos0, 0
         io.x_fp32 = 1 if ws.x.dtype == torch.float32 else 0
         io.last_rows_only = 1 if last_rows else 0
+        if kv_scales is not None:                                  # the FP8 KV cache (decode): kc / vc hold codes (byte strides), one fp32 scale per row beside them
+            ks, vs = kv_scales
+            io.kv_fp8, io.k_scale, io.v_scale, io.scale_layer_stride = 1, ks[0, b0].data_ptr(), vs[0, b0].data_ptr(), ks.stride(0)
         ops.llama_layers(self._layer_table(), len(self.model.layers), io, self.device)
 
     # ------------------------------------------------------------------ one pass over the layers
     def _layers(self, ws: _Workspace, B: int, S: int, kc: torch.Tensor, vc: torch.Tensor, b0: int, Tmax: int, pos0: int,
                 pos_dev: Optional[torch.Tensor], vt: Optional[torch.Tensor], pos_ids: Optional[torch.Tensor] = None,
                 kv_start: Optional[torch.Tensor] = None, key_mask: Optional[torch.Tensor] = None, t0: int = 0,
-                row_off: Optional[torch.Tensor] = None, last_rows: bool = False):
+                row_off: Optional[torch.Tensor] = None, last_rows: bool = False, kv_scales=None):
         """x (ws.x[:B*S]) -> x after all layers.  Prefill when vt is given (S rows per sequence, positions pos0..),
         decode otherwise (S == 1, position read from pos_dev).  kc/vc: [L, Btot, Hk, Tmax, d]; rows b0..b0+B.
         The RAGGED decode batch (generate_many(coalesce=True)): sequences of different prompt lengths are right-aligned in one cache - a
@@ -448,10 +526,19 @@ class GenerationEngine:
         pos_ids (int32 [B, S]) / kv_start (int32 [B]) / key_mask (int32 [B, words], ops.pack_key_mask): forward()'s position_ids and
         attention_mask (unified_llama.py:149-160) - explicit rotary positions, a per-sequence first visible key (left padding) or a
         visibility bit per key (any other mask); they select the per-launch sequence below (RoPE as its own pass), which is not the
-        benchmarked path."""
+        benchmarked path.
+        kv_scales = (k_scale, v_scale) fp32 [L, Btot, Hk, Tmax]: kc / vc are the uint8 codes of the FP8 KV cache (decode steps only): the
+        projection leaves its raw row and crab_attn_decode_fp8 rotates, quantises, appends and attends (row_off = its first visible key)."""
         c = self.cfg
         H, Hk, d = c.num_attention_heads, c.num_key_value_heads, c.head_dim
         M = B * S
+        if kv_scales is not None:
+            if vt is not None or S != 1:
+                raise NotImplementedError('kv_cache_dtype="fp8_e4m3": a prefill runs in bf16 into the staging block (GenerationEngine._prefill_chunk), the fp8 cache takes decode steps only')
+            if pos_ids is not None or kv_start is not None or key_mask is not None:
+                raise NotImplementedError('kv_cache_dtype="fp8_e4m3": the masked one-token step of forward() (position_ids / attention_mask; crab_attn_decode_keymask) has no fp8 form')
+            if kc.dtype != torch.uint8 or not (kc.is_contiguous() and vc.is_contiguous() and kv_scales[0].is_contiguous() and kv_scales[1].is_contiguous()):
+                raise ValueError("fp8 KV cache: contiguous uint8 codes and fp32 scales expected")
         x, h, qkv, att, act = ws.x[:M], ws.h[:M], ws.qkv[:M], ws.att[:M], ws.act[:M]
         tab = self._rope_tab(Tmax)
         scale = 1.0 / math.sqrt(d)
@@ -473,11 +560,11 @@ class GenerationEngine:
                                                          (pos_ids is None or (pos_ids.dtype == torch.int32 and pos_ids.stride(1) == 1))))
         last_rows = bool(last_rows) and vt is not None and S > 1 and key_mask is None and pos_dev is None
         if NATIVE_LAYERS and not timed and native_ok and contig and (vt is not None or S == 1):
-            self._layers_native(ws, B, S, kc, vc, b0, Tmax, pos0, pos_dev, vt, t0, row_off, pos_ids, kv_start, last_rows)
+            self._layers_native(ws, B, S, kc, vc, b0, Tmax, pos0, pos_dev, vt, t0, row_off, pos_ids, kv_start, last_rows, kv_scales)
             return x, h
         u_qkv = None                                   # router output for the q|k|v group when a producer epilogue made it
         # small batch: the projection leaves its raw row, ONE launch does RoPE + KV append + split-context attention (as csrc/llama_layer.hip)
-        aw = self._attn_scratch(ws, B) if (vt is None and S == 1 and not masked and row_off is None and contig) else None
+        aw = self._attn_scratch(ws, B) if (vt is None and S == 1 and not masked and row_off is None and contig and kv_scales is None) else None
         fuse_attn = aw is not None and aw.numel() >= ops.attn_decode_rope_bytes(B, H, d)
         for li, layer in enumerate(layers):
             a, m = layer.self_attn, layer.mlp
@@ -488,7 +575,7 @@ class GenerationEngine:
             if last_rows and li + 1 == len(layers):
                 self._last_layer_last_rows(ws, layer, B, S, kcl, vcl, lcontig, Tmax, pos0, vt, pos_ids, kv_start, u_qkv)
                 return x, h
-            if fuse_attn:
+            if fuse_attn or kv_scales is not None:
                 a._qkv(h, out=qkv, t_buf=ws.t, u_buf=ws.u, u_ready=u_qkv)
             elif vt is None and S == 1 and lcontig and not masked:
                 # decode: RoPE + KV append ride on the q|k|v projection (fused into its split-K reduction when it has one)
@@ -512,6 +599,9 @@ class GenerationEngine:
                 ops.attn_fwd(qkv, kcl, vt, att, q_strides=(S * ldq, d, ldq), k_strides=(Hk * Tmax * d, Tmax * d, d),
                              vt_strides=(Hk * d * Sp, d * Sp, Sp), o_strides=(S * H * d, H * d), B=B, H=H, Hk=Hk, Sq=S,
                              Skv=pos0 + S, head_dim=d, scale=scale, causal=True, kv_start=kv_start, key_mask=key_mask)
+            elif kv_scales is not None:
+                ops.attn_decode_fp8(qkv, tab, kcl, vcl, kv_scales[0][li, b0:b0 + B], kv_scales[1][li, b0:b0 + B], att, B, H, Hk, d, Tmax, pos0, scale,
+                                    pos_dev=pos_dev, kv_start=row_off)
             elif fuse_attn:
                 ops.attn_decode_rope(qkv, tab, kcl, vcl, att, B, H, Hk, d, Tmax, pos0, scale, pos_dev=pos_dev, workspace=aw)
             else:
@@ -615,7 +705,8 @@ class GenerationEngine:
         B = st.B
         ws = st.ws
         ops.embedding(st.cur_ids, self.model.embed_tokens.weight, out=ws.x[:B])
-        x, hfin = self._layers(ws, B, 1, st.kc, st.vc, 0, st.Tmax, 0, st.pos_dev, None, row_off=st.row_off)
+        x, hfin = self._layers(ws, B, 1, st.kc, st.vc, 0, st.Tmax, 0, st.pos_dev, None, row_off=st.row_off,
+                               kv_scales=(st.ks, st.vs) if st.ks is not None else None)
         ops.gemm(hfin, self.lm_head.weight, out=st.logits)
         if st.want_hidden:
             ops.copy_rows(hfin, st.hn, B, hfin.shape[1])
@@ -642,7 +733,9 @@ class GenerationEngine:
         dev = self.device
         D = self.cfg.hidden_size
         Tmax = _round_up(S + max_new_tokens, 64)
-        kc, vc = self.alloc_cache(B, Tmax, slot=slot)
+        kv = self.alloc_cache(B, Tmax, slot=slot)
+        kc, vc = kv[0], kv[1]
+        ks, vs = (kv[2], kv[3]) if len(kv) == 4 else (None, None)          # fp8 mode: the row scales beside the codes
         V = self.lm_head.weight.shape[0]
         if isinstance(eos_token_id, (list, tuple)):            # HF accepts a list of stop ids (Qwen2-7B-Instruct's generation_config holds two); the device loop carries one
             if len(set(int(e) for e in eos_token_id)) > 1:
@@ -656,12 +749,14 @@ class GenerationEngine:
         key = (B, Tmax, max_new_tokens, eos, pad, int(min_new_tokens), bool(return_hidden), kc.data_ptr(), vc.data_ptr(), id(ws),
                tab.data_ptr(), self.lm_head.weight.data_ptr(), self.model.embed_tokens.weight.data_ptr(),
                self.model.layers[0].self_attn._qkv.W.data_ptr(),
-               self.model.layers[0].self_attn._qkv.RA is not None, sampling, bool(ragged))
+               self.model.layers[0].self_attn._qkv.RA is not None, sampling, bool(ragged),
+               self._kv_mode, ks.data_ptr() if ks is not None else 0, vs.data_ptr() if vs is not None else 0)
         st = self._dec.get(slot)
         if st is None or st.key != key:
             st = _DecodeState()
             st.key, st.graph = key, None
             st.B, st.Tmax, st.kc, st.vc, st.slot, st.ws = B, Tmax, kc, vc, slot, ws
+            st.ks, st.vs = ks, vs
             st.logits = torch.empty((B, V), device=dev, dtype=torch.float32)
             st.hn = torch.empty((B, D), device=dev, dtype=BF16)
             st.cur_ids = torch.empty((B,), device=dev, dtype=torch.int64)
@@ -678,6 +773,20 @@ class GenerationEngine:
         st.pos_dev.fill_(S - 1); st.step_dev.zero_()
         return st
 
+    def _prefill_chunk(self, st: "_DecodeState", emb: torch.Tensor, b0: int, t0: int = 0, pos_ids=None, kv_start=None):
+        """Prefill the sequences b0 .. b0 + n of a decode state (first logits / hidden rows into st.logits / st.hn).  bf16 mode: straight into the
+        cache at slots t0 ...  fp8 mode: exactly the same prefill into the bf16 staging block (slots 0 ..; the first token's logits equal the
+        bf16 mode's bit for bit), then crab_kv_quant_fp8 moves the rows to slots t0 .. of the fp8 cache; kv_start (the front padding of a merged
+        ragged wave) doubles as the quantiser's row_off: the padded rows are neither read nor written."""
+        n, S = emb.shape[0], emb.shape[1]
+        lo, hn = st.logits[b0:b0 + n], st.hn[b0:b0 + n]
+        if st.ks is None:
+            self.prefill(emb, st.kc, st.vc, b0=b0, logits_out=lo, hn_out=hn, pos_ids=pos_ids, kv_start=kv_start, t0=t0)
+            return
+        sk, sv = self._staging(n, S)
+        self.prefill(emb, sk, sv, b0=0, logits_out=lo, hn_out=hn, pos_ids=pos_ids, kv_start=kv_start)
+        ops.kv_quant_fp8(sk, sv, st.kc, st.vc, st.ks, st.vs, b0=b0, t0=0, t_dst=t0, S=S, row_off=kv_start)
+
     def _start(self, embeds: torch.Tensor, max_new_tokens: int, eos_token_id, pad_token_id, min_new_tokens: int, prefill_chunk: int,
                return_hidden: bool, slot: int, sink=None, sampling=None) -> "_DecodeState":
         """Allocate the decode state of one group of sequences, prefill it and select its first token."""
@@ -688,7 +797,7 @@ class GenerationEngine:
             ([B % prefill_chunk] if B % prefill_chunk else [])
         b0 = 0
         for n in chunks:
-            self.prefill(embeds[b0:b0 + n], st.kc, st.vc, b0=b0, logits_out=st.logits[b0:b0 + n], hn_out=st.hn[b0:b0 + n])
+            self._prefill_chunk(st, embeds[b0:b0 + n], b0)
             b0 += n
         if sink is not None:
             sink(st)
@@ -718,8 +827,7 @@ class GenerationEngine:
                     if lo < hi:
                         pieces.append(e[lo - starts[j]:hi - starts[j]])
                 emb = pieces[0] if len(pieces) == 1 else torch.cat(pieces, 0)
-                self.prefill(emb, st.kc, st.vc, b0=b0 + c0, logits_out=st.logits[b0 + c0:b0 + c0 + n], hn_out=st.hn[b0 + c0:b0 + c0 + n],
-                             t0=Smax - Ss[g])
+                self._prefill_chunk(st, emb, b0 + c0, t0=Smax - Ss[g])
                 c0 += n
             b0 += n_span
             g = g1 + 1
@@ -757,8 +865,7 @@ class GenerationEngine:
             self._rope_tab(st.Tmax)
             b0 = 0
             for n in self.plan_prefill_chunks(Bt, Smax):
-                self.prefill(emb[b0:b0 + n], st.kc, st.vc, b0=b0, logits_out=st.logits[b0:b0 + n], hn_out=st.hn[b0:b0 + n],
-                             pos_ids=pos_ids[b0:b0 + n], kv_start=st.row_off[b0:b0 + n])
+                self._prefill_chunk(st, emb[b0:b0 + n], b0, pos_ids=pos_ids[b0:b0 + n], kv_start=st.row_off[b0:b0 + n])
                 b0 += n
             del emb
             self.last_ragged_prefill = "merged"
@@ -792,9 +899,10 @@ class GenerationEngine:
     def generate(self, embeds: torch.Tensor, max_new_tokens: int, eos_token_id: Optional[int] = None,
                  pad_token_id: Optional[int] = None, min_new_tokens: int = 0, prefill_chunk: int = 0, use_graph: bool = True,
                  return_step_logits: bool = False, return_hidden: bool = False, decode_streams: int = 1,
-                 return_first_logits: bool = False, sampling=None):
-        return self._retry_after_eviction(self._generate, embeds, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, prefill_chunk, use_graph,
-                                          return_step_logits, return_hidden, decode_streams, return_first_logits, sampling)
+                 return_first_logits: bool = False, sampling=None, kv_cache_dtype: Optional[str] = None):
+        """kv_cache_dtype: "bf16" / "fp8_e4m3" for this call (None: the engine's); see _generate for the rest."""
+        return self._with_kv_mode(kv_cache_dtype, self._retry_after_eviction, self._generate, embeds, max_new_tokens, eos_token_id, pad_token_id,
+                                  min_new_tokens, prefill_chunk, use_graph, return_step_logits, return_hidden, decode_streams, return_first_logits, sampling)
 
     def _generate(self, embeds: torch.Tensor, max_new_tokens: int, eos_token_id: Optional[int] = None,
                   pad_token_id: Optional[int] = None, min_new_tokens: int = 0, prefill_chunk: int = 0, use_graph: bool = True,
@@ -905,9 +1013,10 @@ class GenerationEngine:
     def generate_many(self, embeds_list: List[torch.Tensor], max_new_tokens: int, eos_token_id: Optional[int] = None,
                       pad_token_id: Optional[int] = None, min_new_tokens: int = 0, use_graph: bool = True, sampling=None,
                       return_first_logits: bool = False, coalesce: bool = False, max_rows: Optional[int] = None,
-                      return_step_logits: bool = False, return_hidden: bool = False):
-        return self._retry_after_eviction(self._generate_many, embeds_list, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling,
-                                          return_first_logits, coalesce, max_rows, return_step_logits, return_hidden)
+                      return_step_logits: bool = False, return_hidden: bool = False, kv_cache_dtype: Optional[str] = None):
+        """kv_cache_dtype: "bf16" / "fp8_e4m3" for this call (None: the engine's); see _generate_many for the rest."""
+        return self._with_kv_mode(kv_cache_dtype, self._retry_after_eviction, self._generate_many, embeds_list, max_new_tokens, eos_token_id, pad_token_id,
+                                  min_new_tokens, use_graph, sampling, return_first_logits, coalesce, max_rows, return_step_logits, return_hidden)
 
     def _generate_many(self, embeds_list: List[torch.Tensor], max_new_tokens: int, eos_token_id: Optional[int] = None,
                        pad_token_id: Optional[int] = None, min_new_tokens: int = 0, use_graph: bool = True, sampling=None,

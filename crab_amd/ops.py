@@ -504,6 +504,47 @@ def attn_decode_rope(qkv, rope_tab, k_cache, v_cache, o, B, H, Hk, head_dim, Tma
     return o
 
 
+def kv_quant_fp8(k_src, v_src, k_codes, v_codes, k_scale, v_scale, b0: int = 0, t0: int = 0, t_dst: int = 0, S: Optional[int] = None,
+                 row_off: Optional[torch.Tensor] = None):
+    """bf16 cache block [L, Bc, Hk, T_src, d] (rows t0 .. t0 + S - 1 live) -> the FP8 KV cache: e4m3fn codes uint8 [L, B, Hk, Tmax, d] and fp32 row
+    scales [L, B, Hk, Tmax], sequences b0 .. b0 + Bc - 1, slots t_dst .. t_dst + S - 1 (crab_kv_quant_fp8; include/crab_hip.h for the format).
+    row_off (int32 [Bc]): the first row_off[b] rows of sequence b are front padding - neither read nor written."""
+    d = _dev(k_src)
+    _chk_bf16(k_src, v_src)
+    L, Bc, Hk, Tsrc, hd = k_src.shape
+    Tmax = k_codes.shape[3]
+    if k_codes.dtype != torch.uint8 or v_codes.dtype != torch.uint8 or k_scale.dtype != torch.float32 or v_scale.dtype != torch.float32:
+        raise _lib.CrabHipError("kv_quant_fp8: codes are uint8, scales float32")
+    for t in (k_src, v_src, k_codes, v_codes, k_scale, v_scale):
+        if not t[0].is_contiguous():
+            raise _lib.CrabHipError("kv_quant_fp8: every layer of the block / cache must be contiguous")
+    if (v_src.shape != k_src.shape or v_codes.shape != k_codes.shape or tuple(k_codes.shape[i] for i in (0, 2, 4)) != (L, Hk, hd) or
+            tuple(k_scale.shape) != tuple(k_codes.shape[:4]) or v_scale.shape != k_scale.shape or b0 < 0 or b0 + Bc > k_codes.shape[1]):
+        raise _lib.CrabHipError("kv_quant_fp8: the block [L, Bc, Hk, T_src, d], the codes [L, B, Hk, Tmax, d] and the scales [L, B, Hk, Tmax] do not match")
+    if row_off is not None and (row_off.dtype != torch.int32 or row_off.dim() != 1 or row_off.shape[0] < Bc or not row_off.is_contiguous()):
+        raise ValueError("row_off must be a contiguous int32 [Bc] tensor")
+    S = Tsrc - t0 if S is None else S
+    _lib.check(_lib.load().crab_kv_quant_fp8(_lib.ctx(d), _stream(), _p(k_src), _p(v_src), k_src.stride(0), Tsrc, t0, _p(k_codes), _p(v_codes),
+                                             k_codes.stride(0), _p(k_scale), _p(v_scale), k_scale.stride(0), L, Bc, Hk, hd, Tmax, b0, t_dst, S,
+                                             _p(row_off)), d)
+
+
+def attn_decode_fp8(qkv, rope_tab, k_codes, v_codes, k_scale, v_scale, o, B, H, Hk, head_dim, Tmax, pos0, scale, pos_dev=None, kv_start=None):
+    """One decode step's attention over the FP8 KV cache of ONE layer (codes uint8 [B, Hk, Tmax, d], scales fp32 [B, Hk, Tmax]) from the raw packed
+    q|k|v rows: RoPE of q / new k at slot - kv_start[b], quantised append at slot = pos0 + pos_dev[0], attention over kv_start[b] .. slot."""
+    d = _dev(qkv)
+    _chk_bf16(qkv, o)
+    if k_codes.dtype != torch.uint8 or v_codes.dtype != torch.uint8 or k_scale.dtype != torch.float32 or v_scale.dtype != torch.float32:
+        raise _lib.CrabHipError("attn_decode_fp8: codes are uint8, scales float32")
+    if not (k_codes.is_contiguous() and v_codes.is_contiguous() and k_scale.is_contiguous() and v_scale.is_contiguous()):
+        raise _lib.CrabHipError("attn_decode_fp8: the layer's codes / scales must be contiguous")
+    if tuple(k_codes.shape) != (B, Hk, Tmax, head_dim) or v_codes.shape != k_codes.shape or tuple(k_scale.shape) != (B, Hk, Tmax) or v_scale.shape != k_scale.shape:
+        raise _lib.CrabHipError("attn_decode_fp8: codes [B, Hk, Tmax, d] / scales [B, Hk, Tmax] expected")
+    _lib.check(_lib.load().crab_attn_decode_fp8(_lib.ctx(d), _stream(), _p(qkv), qkv.stride(0), _p(rope_tab), _p(k_codes), _p(v_codes), _p(k_scale),
+                                                _p(v_scale), _p(o), o.stride(0), B, H, Hk, head_dim, Tmax, pos0, _p(pos_dev), scale, _p(kv_start)), d)
+    return o
+
+
 def enc_layer(kind: str, w, io, device):
     """crab_clip_layer / crab_beats_layer / crab_qformer_layer: one encoder layer's launch sequence in one call."""
     d = device.index or 0

@@ -59,7 +59,7 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
         self.vocab_size = config.vocab_size
         self.lm_head = LMHead(config.hidden_size, config.vocab_size, device)
         self.is_avs_task = False
-        self._engine = GenerationEngine(self.model, self.lm_head)
+        self._engine = GenerationEngine(self.model, self.lm_head, kv_cache_dtype=kwargs.get("kv_cache_dtype", "bf16"))   # "fp8_e4m3": the opt-in FP8 KV cache
         self._past = None
 
     # ------------------------------------------------------------------ plumbing
@@ -160,6 +160,15 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
             raise NotImplementedError("training losses / AVS forward are outside the inference hot path")
         eng = self._engine
         dev = self.device
+        kvd = eng.check_kv_cache_dtype(kwargs.get("kv_cache_dtype") or eng.kv_cache_dtype)
+        if kvd != "bf16" and (use_cache or past_key_values is not None):
+            # the FP8 KV cache is generate()'s: a caller-held cache (and the masked one-token shortcut over it, crab_attn_decode_keymask) stays bf16
+            raise NotImplementedError(f'forward(use_cache=True / past_key_values) with kv_cache_dtype={kvd!r}: a caller-held KV cache is bf16 only '
+                                      '(the FP8 cache serves generate() / generate_batches() / generate_avs())')
+        if kvd != "bf16":
+            return eng._with_kv_mode("bf16", self.forward, batch_input_ids, batch_labels, batch_X_modals, batch_task_names, input_ids, attention_mask,
+                                     position_ids, past_key_values, inputs_embeds, labels, use_cache, output_attentions, output_hidden_states,
+                                     return_dict, **{**kwargs, "kv_cache_dtype": "bf16"})      # no cache is kept: the scratch cache of this pass is bf16
         if input_ids is not None and input_ids.shape[1] == 1 and past_key_values is not None:
             kc, vc, n = past_key_values
             if n >= kc.shape[3]:
@@ -237,6 +246,7 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
     def generate(self, batch_input_ids=None, batch_labels=None, batch_X_modals=None, batch_task_names=None, **kwargs):
         """unified_llama.py:244-267.  kwargs understood (HF names): max_new_tokens, min_new_tokens, eos_token_id,
         pad_token_id, use_cache, do_sample (+ temperature, top_k, top_p, seed), output_logits / return_dict_in_generate (parity audits),
+        kv_cache_dtype ("bf16" | "fp8_e4m3": the KV cache of this call, default the engine's - GenerationEngine(kv_cache_dtype=...)),
         output_first_logits (ids + the fp32 logits of the first generated position, [B, V]: the record the multi-GPU eval gathers),
         inputs_embeds (skip prepare_multimodal_inputs)."""
         self._check_generate_kwargs(kwargs)
@@ -259,7 +269,7 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
                                     min_new_tokens=int(kwargs.get("min_new_tokens", 0) or 0),
                                     prefill_chunk=int(kwargs.get("prefill_chunk", 0)), use_graph=kwargs.get("use_graph", True),
                                     return_step_logits=want_logits, decode_streams=int(kwargs.get("decode_streams", 1)),
-                                    return_first_logits=want_first, sampling=sampling)
+                                    return_first_logits=want_first, sampling=sampling, kv_cache_dtype=kwargs.get("kv_cache_dtype"))
         if want_logits or want_first:
             res = list(res)
             out = type("GenerateOutput", (), {})()
@@ -305,7 +315,8 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
         pad = kwargs.get("pad_token_id", self.model.pad_token_id if self.model.pad_token_id is not None else eos)
         return self._engine.generate_many(embeds, int(kwargs.get("max_new_tokens", 20)), eos_token_id=eos, pad_token_id=pad,
                                           min_new_tokens=int(kwargs.get("min_new_tokens", 0) or 0), use_graph=kwargs.get("use_graph", True),
-                                          sampling=sampling, return_first_logits=want_first, coalesce=coalesce, max_rows=max_rows)
+                                          sampling=sampling, return_first_logits=want_first, coalesce=coalesce, max_rows=max_rows,
+                                          kv_cache_dtype=kwargs.get("kv_cache_dtype"))
 
     # HF generate() arguments that would CHANGE what is decoded and that this path does not implement: refused by name instead of ignored
     # (name -> the value that means "off").  Everything the reference's loops pass (use_cache, max_new_tokens; do_sample & co. from the
@@ -414,7 +425,8 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
         pad = kwargs.get("pad_token_id", self.model.pad_token_id if self.model.pad_token_id is not None else eos)
         outs = self._engine.generate_many(embeds, int(kwargs.get("max_new_tokens", 20)), eos_token_id=eos, pad_token_id=pad,
                                           min_new_tokens=int(kwargs.get("min_new_tokens", 0) or 0), use_graph=kwargs.get("use_graph", True),
-                                          sampling=sampling, coalesce=True, max_rows=max_rows, return_hidden=True)
+                                          sampling=sampling, coalesce=True, max_rows=max_rows, return_hidden=True,
+                                          kv_cache_dtype=kwargs.get("kv_cache_dtype"))
         return inputs, outs
 
     def _avs_segment(self, samples, inputs, outs, chosen):

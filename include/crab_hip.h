@@ -286,6 +286,33 @@ int crab_attn_decode_rope(crab_ctx* ctx, void* stream, const void* qkv, int64_t 
                           void* v_cache, void* o, int64_t ldo, int B, int H, int Hk, int d, int Tmax, int pos0,
                           const int32_t* pos_dev, float scale, void* workspace, int64_t workspace_bytes);
 
+/* ---- FP8 KV cache (ABI 13; opt-in, crab_llama_io.kv_fp8).  Storage: K (after RoPE) and V as one byte per element, OCP e4m3fn, layout
+ * [L, B, Hk, Tmax, d] like the bf16 cache, plus one fp32 scale per cached row and KV head for K and for V: two arrays [L, B, Hk, Tmax].
+ *     amax = max |x| over the row's d elements (x = the bf16 values the bf16 cache would hold);
+ *     scale = amax / 448.0f (fp32 division); 1.0f when amax == 0; FLT_MIN when the quotient is below FLT_MIN (1 / scale stays finite);
+ *     inv = 1.0f / scale; code = e4m3fn_rne(x * inv); the value read back is float(code) * scale.
+ * A cached row costs d + 4 bytes instead of 2 d.  Prefill is unchanged and attends bf16 K / V; decode attends the fp8 cache for EVERY key,
+ * the one appended in the same step included, so a decode step's output is a function of the cache contents and the raw q|k|v row alone.
+ *
+ * crab_kv_quant_fp8: the cache append of modeling_llama.py:408-412 for a prefilled block, in the fp8 format.  k_src / v_src: a bf16 cache
+ * block [L, Bc, Hk, T_src, d] (src_layer_stride elements between layers) whose rows t0 .. t0 + S - 1 of each sequence are live; they are
+ * written as codes + scales to sequences b0 .. b0 + Bc - 1, slots t_dst .. t_dst + S - 1 of the fp8 cache [L, *, Hk, Tmax, d]
+ * (code_layer_stride bytes, scale_layer_stride floats between layers).  row_off (int32 [Bc], may be NULL): sequence b of the block is
+ * front-padded - its rows s < row_off[b] are neither read nor written (the right-aligned ragged cache; crab_llama_io.row_off). */
+int crab_kv_quant_fp8(crab_ctx* ctx, void* stream, const void* k_src, const void* v_src, int64_t src_layer_stride, int T_src, int t0,
+                      void* k_codes, void* v_codes, int64_t code_layer_stride, float* k_scale, float* v_scale,
+                      int64_t scale_layer_stride, int L, int Bc, int Hk, int d, int Tmax, int b0, int t_dst, int S,
+                      const int32_t* row_off);
+/* crab_attn_decode_fp8: one decode step's attention over the fp8 cache (modeling_llama.py:394-452 with q_len == 1; RoPE :204-236, cache
+ * append :408-412), one launch per layer, from the RAW packed q|k|v row of the projection (as crab_attn_decode_rope takes it).  Per (b, h):
+ * q and the new k rotate at position slot - kv_start[b] (slot = pos0 + pos_dev[0]; pos_dev / kv_start may be NULL) and are rounded to
+ * bf16 like the stored form; the new k / v rows are quantised as above and appended at `slot` (codes and scales); the query attends the
+ * cached slots kv_start[b] .. slot - 1 and the DEQUANTISED new row.  One block per (b, h) for any H / Hk; d = 64 or 128.  No host reads:
+ * capturable in a graph. */
+int crab_attn_decode_fp8(crab_ctx* ctx, void* stream, const void* qkv, int64_t ldqkv, const float* rope_tab, void* k_codes,
+                         void* v_codes, float* k_scale, float* v_scale, void* o, int64_t ldo, int B, int H, int Hk, int d, int Tmax,
+                         int pos0, const int32_t* pos_dev, float scale, const int32_t* kv_start);
+
 /* y[M, I] = silu(gu[:, :I]) * gu[:, I:2I]   (modeling_llama.py:269; gate and up packed side by side) */
 int crab_swiglu(crab_ctx* ctx, void* stream, const void* gu, int64_t ldgu, void* y, int64_t ldy, int M, int I);
 
@@ -425,6 +452,14 @@ typedef struct {
      * first B rows and qkv's storage are reused).  Needs S > 1, M = B * S rows of act with ldact >= H * d, qkv storage >= B * D * 4 bytes
      * (true for every decoder: M * ldqkv * 2 bytes).  0: every row through every layer (forward(): all logits). */
     int32_t last_rows_only;
+    /* ABI 13, DECODE only: the FP8 KV cache (crab_kv_quant_fp8 above for the format).  kv_fp8 = 1: k_cache / v_cache point at e4m3fn codes
+     * and cache_layer_stride counts BYTES of codes; k_scale / v_scale: fp32 [L, B, Hk, Tmax], scale_layer_stride floats between layers.  The
+     * q|k|v projection then runs without RoPE and crab_attn_decode_fp8 rotates, appends and attends (row_off = its kv_start); the fused
+     * small-batch split-context launch (attn_ws) is not used.  kv_fp8 = 1 on a prefill call is CRAB_E_INVALID: a prompt is prefilled into
+     * a bf16 block and moved over by crab_kv_quant_fp8.  0: the bf16 cache. */
+    int32_t kv_fp8;
+    float* k_scale; float* v_scale;
+    int64_t scale_layer_stride;
 } crab_llama_io;
 
 int crab_sizeof_llama_layer(void);
