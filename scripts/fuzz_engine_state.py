@@ -62,6 +62,7 @@ def run(model, c, hid, V):
     g = torch.Generator().manual_seed(c["seed"])
     rn = lambda *s: (torch.randn(*s, generator=g) * 0.5).to(BF).cuda()
     out = []
+    kvkw = {"kv_cache_dtype": c["kv"]} if c.get("kv") is not None else {}       # scripts/fuzz_kv_fp8.py's calls name the KV-cache mode (no entry: the engine's)
     if c["kind"] == "generate":
         emb = rn(c["B"], c["S"], hid)
         eos = None
@@ -76,13 +77,13 @@ def run(model, c, hid, V):
         if c["extra"] == "logits": kw["return_step_logits"] = True
         if c["extra"] == "first": kw["return_first_logits"] = True
         try:
-            r = eng.generate(emb, c["n"], **kw)
+            r = eng.generate(emb, c["n"], **kw, **kvkw)
         finally:
             eng.kv_budget_bytes = None
         out = [x.clone() for x in (r if isinstance(r, (tuple, list)) else [r])]
     elif c["kind"] == "batches":
         embs = [rn(b, c["S"][i % 5], hid) for i, b in enumerate(c["sizes"])]
-        r = eng.generate_many(embs, c["n"], eos_token_id=None, pad_token_id=2, coalesce=c["coalesce"], max_rows=c["max_rows"] if c["coalesce"] else None)
+        r = eng.generate_many(embs, c["n"], eos_token_id=None, pad_token_id=2, coalesce=c["coalesce"], max_rows=c["max_rows"] if c["coalesce"] else None, **kvkw)
         for x in r:
             out += [y.clone() for y in (x if isinstance(x, (tuple, list)) else [x])]
     else:

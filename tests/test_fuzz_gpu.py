@@ -1,4 +1,4 @@
-"""Differential fuzz through the C-ABI at random shapes around every dispatch boundary - short fixed-seed runs of the eleven generators under scripts/
+"""Differential fuzz through the C-ABI at random shapes around every dispatch boundary - short fixed-seed runs of the twelve generators under scripts/
 (one process: scripts/fuzz_all.py; the cases are the same on every run):
   fuzz_gemm.py           the GEMM regimes x epilogues against fp32 torch on the same bf16 operands,
   fuzz_attn.py           the attention entry points x masks,
@@ -13,7 +13,11 @@
   fuzz_seg.py            r06: the SegModule helpers, the remaining VQGAN helpers and the eval loops' metrics (counts equal to oracle/metrics_oracle.py),
   fuzz_engine_state.py   r06: random SEQUENCES of generate / generate_many / forward calls on one engine, carried state against fresh state, bit for bit,
   fuzz_model_state.py    r06: the same at the model level (encoders, projectors, splice, engine; changing frames / windows / modality subsets; a side stream),
-  fuzz_vqgan.py          r06: the VQGAN mask tokenizer at random batch and mask sizes against oracle/vqgan_oracle.py (ids equal outside the oracle's own margin).
+  fuzz_vqgan.py          r06: the VQGAN mask tokenizer at random batch and mask sizes against oracle/vqgan_oracle.py (ids equal outside the oracle's own margin),
+  fuzz_kv_fp8.py         the FP8 KV cache: the quantiser bit for bit and the fp8 decode attention per (sequence, head) against fp64 at cached-key counts on
+                         every residue modulo 64, spread row scales, all forms of the slot argument, every documented refusal; one decode step of the
+                         stack on a CPU-built cache against the oracle; generate() / generate_many() cache contents equal to the quantised bf16 cache
+                         under every prefill chunking; call sequences that mix the two modes (tests/test_kv_fp8_host.py pins the coverage of its cases).
 (r05: half the r04 case count here - the suite has a time limit; tests/test_slow_gpu.py runs 8x that (scale 4) under `-m gpu_slow`.)
 A combination outside a stated limit must be REJECTED (CRAB_E_INVALID / CRAB_E_UNSUPPORTED), never computed wrong; outputs sit inside sentinel guards."""
 import os
@@ -24,7 +28,8 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FUZZERS = ["fuzz_gemm.py", "fuzz_attn.py", "fuzz_decoder.py", "fuzz_multimodal.py", "fuzz_rope_epilogue.py", "fuzz_frontend.py", "fuzz_ops.py", "fuzz_seg.py", "fuzz_engine_state.py", "fuzz_model_state.py", "fuzz_vqgan.py"]
+FUZZERS = ["fuzz_gemm.py", "fuzz_attn.py", "fuzz_decoder.py", "fuzz_multimodal.py", "fuzz_rope_epilogue.py", "fuzz_frontend.py", "fuzz_ops.py", "fuzz_seg.py", "fuzz_engine_state.py", "fuzz_model_state.py", "fuzz_vqgan.py",
+           "fuzz_kv_fp8.py"]
 
 
 def test_differential_fuzz():

@@ -478,3 +478,78 @@ def test_full_size_fp8_vs_bf16_mode():
                                                           "steps": 128, "ids_equal": int((ids8 == ids16).sum()), "bf16_operand_floor_rel": 3.4e-3})
     del crab, um
     torch.cuda.empty_cache()
+
+
+# ------------------------------------------------------------------------------------------------------------------ fixed points of scripts/fuzz_kv_fp8.py
+def _fuzzer():
+    """A fresh instance of scripts/fuzz_kv_fp8.py (its failure list is module state): the fixed cases below run through the fuzzer's own checks."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("fuzz_kv_fp8", os.path.join(ROOT, "scripts", "fuzz_kv_fp8.py"))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    return m
+
+
+def test_fp8_entry_points_refuse_what_they_document():
+    """Every documented refusal of crab_kv_quant_fp8 / crab_attn_decode_fp8 and of their wrappers (head_dim 32, H % Hk != 0, pos0 outside the
+    cache, misaligned code / source / q|k|v pointers, an odd row stride, t0 + S > T_src, t_dst + S > Tmax, S = 0, b0 outside the cache, wrong
+    dtypes and shapes): the call raises with the stated message and codes, scales and output keep their contents.  Host-side checks only."""
+    F = _fuzzer()
+    F.run_rejections()
+    assert not F.bad, F.bad
+    assert F.stats["A_reject"] == 21, (F.stats, F.why)
+    assert sum(F.why.values()) == 21 and any("position outside the KV cache" in k for k in F.why), F.why
+
+
+@pytest.mark.parametrize("count", [31, 32, 33, 63, 64, 65, 66, 95, 96, 97, 98, 127, 128, 129, 130])
+@pytest.mark.parametrize("Hk,G,d", [(4, 1, 64), (4, 7, 128)])
+def test_fp8_decode_attention_at_the_group_and_prefetch_boundaries(Hk, G, d, count):
+    """crab_attn_decode_fp8 at the cached-key counts around its structural edges (32 groups, a pair of keys per trip, the two-deep prefetch), one
+    MHA and one G = 7 geometry, on a cache whose K row scales spread over 1e-2 .. 1e2 and V row scales over 1e-3 .. 1e3 (the two keys of a pair
+    carry very different scales), Tmax = 200, q|k|v and output rows with padded strides, the slot given as pos0 alone / pos_dev alone / both
+    non-zero, ragged rows beside the full one: appended codes and scales torch.equal to kv_fp8_ref.quant of the rows crab_qkv_rope_split stores,
+    every other slot and every guard unchanged, the output within TOL_BF16 of fp64 attention over the dequantised rows PER (sequence, head)."""
+    F = _fuzzer()
+    assert F.TOL_BF16 == TOL_BF16
+    B, slot = 3, count + (2 if count % 2 else 0)
+    ks = [slot - count, 0, min(40, slot)]
+    form = F.POS_FORMS[count % 3]
+    case = dict(B=B, Hk=Hk, G=G, d=d, Tmax=200, slot=slot, kv_start=ks if any(ks) else None, counts=[slot - k for k in ks], pos_form=form,
+                pos0=slot if form == "pos0" else 0 if form == "pos_dev" else 17, pad_q=8 if count % 2 else 0, pad_o=64 if count % 4 < 2 else 0,
+                new_k=["plain", "dominant", "zero", "subnormal"][count % 4], new_v=["plain", "zero", "dominant", "subnormal"][(count // 4) % 4], seed=count)
+    F.run_attn(case)
+    print(f"fp8 decode attention Hk={Hk} G={G} d={d} count={count} {form}: worst rel err per head {F.stats['worst_attn']:.3e} (bound {TOL_BF16:.1e})")
+    assert F.stats["A_attn"] == 1 and not F.bad, F.bad
+
+
+def test_chunked_prefill_fills_the_fp8_cache_like_the_bf16_one():
+    """generate(prefill_chunk=2) of 5 sequences in fp8 mode (chunks of 2, 2 and 1 sequences: the staging block reused, the quantiser writing at
+    b0 = 2 and 4): first-token logits torch.equal to the bf16 mode's, and afterwards the codes and scales of every prompt slot of every layer and
+    sequence torch.equal to kv_fp8_ref.quant of the cache rows the bf16 mode leaves under the same chunking - prefill is the same arithmetic in
+    both modes and the quantiser is pinned bit for bit, so a row landing in another sequence / slot / layer shows here."""
+    from crab_amd import ops
+    F = _fuzzer()
+    meta, A, model = _tiny_model("full_tiny_llama")
+    eng = model.base_model.model._engine
+    e2 = A["embeds_bs2"].to(BF)
+    emb = torch.cat([e2, (e2.float() * 0.5).to(BF), -e2[:1]]).cuda()
+    assert emb.shape[0] == 5
+    n, d = 4, eng.cfg.head_dim
+    kw = dict(eos_token_id=None, pad_token_id=2, prefill_chunk=2, return_step_logits=True)
+    eng._dec.clear()
+    ids16, lg16 = eng.generate(emb, n, kv_cache_dtype="bf16", **kw)
+    lg16 = lg16.clone()
+    s16 = F.snapshot(eng)
+    eng._dec.clear()
+    with ops.launch_trace(0) as tr:
+        ids8, lg8 = eng.generate(emb, n, kv_cache_dtype=FP8, **kw)
+    assert tr.launched(f"kv_quant_fp8_kernel<{d}>") == 3, tr.counts
+    s8 = F.snapshot(eng)
+    assert torch.equal(lg16[:, 0], lg8[:, 0]), "first-token logits differ between the modes"
+    assert list(s16) == [0] and s16[0][0] == emb.shape[1] and len(s8[0][2]) == 4
+    assert F.cache_mismatch(s16, s8) is None, F.cache_mismatch(s16, s8)
+    # the check sees a row in the wrong sequence: swap two sequences of the fp8 snapshot
+    perm = [1, 0, 2, 3, 4]
+    swapped = {0: (s8[0][0], s8[0][1], [t[:, perm] for t in s8[0][2]])}
+    assert F.cache_mismatch(s16, swapped) is not None
+    assert eng.kv_cache_dtype == "bf16"

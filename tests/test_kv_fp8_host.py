@@ -156,3 +156,119 @@ def test_sharp_fixture_is_not_too_soft_for_the_fp8_token_id_test():
     exempt, total, worst = sharp_exemptions("sharp_tiny_llama")
     print(f"sharp_tiny_llama: {int(exempt.sum())} of {total} steps exempt; largest per-step fp8-emulation distance {worst:.4f}")
     assert int(exempt.sum()) * 2 <= total, "fixture too soft"
+
+
+# ------------------------------------------------------------------------------------------------------------------ scripts/fuzz_kv_fp8.py, host side
+# The cases the FP8 KV-cache fuzzer generates AT THE COUNT THE GPU SUITE RUNS (scripts/fuzz_all.py at scale 0.5) cover the edges the fuzzer
+# exists for - a later cut of the case count that drops one fails here, without a GPU - and its fp64 attention reference agrees with the
+# oracle's attention.
+import ast
+import importlib.util
+import math
+
+
+def _fuzzer():
+    spec = importlib.util.spec_from_file_location("fuzz_kv_fp8", os.path.join(ROOT, "scripts", "fuzz_kv_fp8.py"))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    return m
+
+
+def _suite_run():
+    """(cases, seed) of fuzz_kv_fp8.py in scripts/fuzz_all.py's RUNS, read from its source (importing the file would run the fuzzers)."""
+    with open(os.path.join(ROOT, "scripts", "fuzz_all.py")) as f:
+        tree = ast.parse(f.read())
+    runs = next(ast.literal_eval(n.value) for n in ast.walk(tree) if isinstance(n, ast.Assign) and getattr(n.targets[0], "id", "") == "RUNS")
+    assert runs[-1][0] == "fuzz_kv_fp8.py", "appended last: the other fuzzers keep their seeds and order"
+    return runs[-1][1], runs[-1][2]
+
+
+def _suite_cases():
+    cases, seed = _suite_run()
+    return _fuzzer().make_cases(max(1, int(cases * 0.5)), seed)        # tests/test_fuzz_gpu.py runs fuzz_all.py at scale 0.5
+
+
+def test_case_generation_is_deterministic_and_needs_no_gpu():
+    F = _fuzzer()
+    cases, seed = _suite_run()
+    assert F.make_cases(cases // 2, seed) == F.make_cases(cases // 2, seed)
+    assert F.make_cases(cases // 2, seed) != F.make_cases(cases // 2, seed + 1)
+
+
+def test_part_a_covers_the_kernel_edges_at_the_suite_count():
+    F = _fuzzer()
+    C = _suite_cases()
+    attn, quant = C["attn"], C["quant"]
+    counts = {n for c in attn for n in c["counts"]}
+    assert {n % 64 for n in counts} == set(range(64)), sorted(set(range(64)) - {n % 64 for n in counts})
+    assert set(F.BOUNDARY_COUNTS) <= counts, sorted(set(F.BOUNDARY_COUNTS) - counts)
+    assert F.BOUNDARY_COUNTS == [0, 1, 31, 32, 33, 63, 64, 65, 95, 96, 97, 127, 128, 129]
+    assert {c["G"] for c in attn} == {1, 2, 4, 7, 8} and {c["d"] for c in attn} == {64, 128}
+    assert {c["Hk"] for c in attn} == {1, 2, 4, 8} and {c["B"] for c in attn} == {1, 2, 3, 8, 40, 130}
+    assert {c["pos_form"] for c in attn} == {"pos0", "pos_dev", "both"}
+    assert all(c["pos0"] > 0 and c["pos0"] < c["slot"] for c in attn if c["pos_form"] == "both")
+    assert any(c["B"] >= 100 for c in attn)
+    assert any(c["kv_start"] is not None and 0 in c["counts"][1:] for c in attn), "a row with zero cached keys beside rows that have some"
+    assert any(c["kv_start"] is None for c in attn) and any(c["pad_q"] for c in attn) and any(c["pad_o"] for c in attn)
+    assert any(t % 64 for t in {c["Tmax"] for c in attn}) and {c["Tmax"] for c in attn} == {64, 128, 200, 960}
+    assert {c["new_k"] for c in attn} >= {"dominant", "zero", "subnormal"} and {c["new_v"] for c in attn} >= {"dominant", "zero", "subnormal"}
+    for c in attn:                                       # every case stays inside its cache
+        assert 0 <= c["slot"] < c["Tmax"] and all(0 <= n <= c["slot"] for n in c["counts"]) and len(c["counts"]) == c["B"]
+    assert {c["d"] for c in quant} == {64, 128} and any(c["row_off"] is None for c in quant)
+    assert any(c["row_off"] and 0 in c["row_off"] and c["S"] - 1 in c["row_off"] for c in quant)
+    assert any((c["L"] * c["Bc"] * c["Hk"] * c["S"]) % (256 // (c["d"] // 8)) for c in quant), "a row total that is not a multiple of the rows per block"
+    for c in quant:
+        assert c["t0"] + c["S"] <= c["Tsrc"] and c["t_dst"] + c["S"] <= c["Tmax"] and c["b0"] + c["Bc"] <= c["B"]
+        assert c["row_off"] is None or all(0 <= o < c["S"] for o in c["row_off"])
+    assert len(attn) > len(quant) > len(C["step"]) >= len(C["gen"]), "part A gets the bulk"
+
+
+def test_parts_b_c_d_cover_their_edges_at_the_suite_count():
+    C = _suite_cases()
+    step = C["step"]
+    assert {c["B"] for c in step} >= {1, 3, 16, 17, 40, 128, 130, 256, 260}, "a batch size in every decode GEMM regime"
+    assert any(c["row_off"] for c in step) and any(not c["row_off"] for c in step)
+    assert {c["cfg"]["d"] for c in step} == {64, 128} and any(c["cfg"]["qwen"] for c in step) and any(not c["cfg"]["qwen"] for c in step)
+    shapes = [s for c in C["gen"] for s in c["shapes"]]
+    for k in (1, 7):
+        assert any(k in s["chunks"] and s["B"] > k for s in shapes), f"more than one prefill chunk with prefill_chunk={k}"
+    assert any(s["B"] // 2 in s["chunks"] and s["B"] // 2 >= 1 and s["B"] >= 2 for s in shapes)
+    assert any(s["B"] >= 100 for s in shapes) and any(s["streams2"] for s in shapes)
+    assert all(len(set(c["ragged"]["S"])) > 1 for c in C["gen"]), "ragged waves need groups of different prompt lengths"
+    calls = C["calls"]
+    mode, seen, visited = "bf16", {}, False
+    for c in calls:
+        mode = c.get("engine") or mode
+        if c["kind"] != "generate": continue
+        seen.setdefault((c["B"], c["S"], c["n"]), []).append(c["kv"] or mode)
+    for modes in seen.values():
+        s = "".join("f" if m == "fp8_e4m3" else "b" for m in modes)
+        visited = visited or "bfb" in s.replace("bb", "b").replace("ff", "f")
+    assert visited, "one shape visited bf16 -> fp8 -> bf16"
+    assert any(c.get("engine") == "fp8_e4m3" for c in calls) and any(c["kind"] == "forward" for c in calls) and any(c["kind"] == "batches" for c in calls)
+    assert any(c.get("kv") is None and c["kind"] == "generate" for c in calls), "calls that take the engine's mode"
+
+
+def test_fp64_attention_reference_agrees_with_the_oracle():
+    """fuzz_kv_fp8.attention_fp64 (grouped-query heads, a per-sequence visibility mask) against oracle.crab_oracle's softmax attention, sequence
+    by sequence over its visible keys; head_rel_err is tests.util.rel_err's measure applied per (sequence, head)."""
+    from oracle import crab_oracle as O
+    from tests.util import rel_err
+    F = _fuzzer()
+    g = torch.Generator().manual_seed(3)
+    B, Hk, G, d, T = 3, 2, 2, 64, 21
+    H = Hk * G
+    q, K, V = torch.randn(B, H, d, generator=g), torch.randn(B, Hk, T, d, generator=g), torch.randn(B, Hk, T, d, generator=g) * 3
+    first = [0, 5, 20]
+    vis = torch.arange(T)[None] >= torch.tensor(first)[:, None]
+    got = F.attention_fp64(q, K, V, vis, d ** -0.5)
+    assert got.dtype == torch.float64
+    for b in range(B):
+        kk, vv = (x[b, :, first[b]:].repeat_interleave(G, 0).transpose(0, 1).reshape(1, T - first[b], H * d) for x in (K, V))
+        ref = O._mha(q[b].reshape(1, 1, H * d), kk, vv, H, 1.0 / math.sqrt(d))
+        assert (got[b].reshape(-1).float() - ref.reshape(-1)).abs().max().item() <= 2e-6 * ref.abs().max().item()
+    a, r = torch.randn(2, 3, 8, generator=g), torch.randn(2, 3, 8, generator=g)
+    e = F.head_rel_err(a, r)
+    for b in range(2):
+        for h in range(3):
+            assert abs(e[b, h].item() - rel_err(a[b, h], r[b, h])) <= 1e-6 * e[b, h].item()
