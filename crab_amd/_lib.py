@@ -198,6 +198,9 @@ SYMBOLS = {
     "crab_greedy_select": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _i64, _vp, _vp, _i, _i, _i]),
     "crab_advance": (_i, [_vp, _vp, _vp, _vp]),
     "crab_sample_select": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _i64, _vp, _vp, _i, _i, _i, _f, _i, _f, C.c_uint64]),
+    "crab_lm_head_xent_workspace": (_i64, [_i, _i]),
+    "crab_lm_head_xent": (_i, [_vp, _vp, _vp, _i64, _vp, _i, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _i64]),
+    "crab_xent_reduce": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "crab_im2col3x3": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i]),
     "crab_pixel_shuffle2x": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i]),
     "crab_bilinear": (_i, [_vp, _vp, _vp, _i, _i64, _i64, _i64, _i, _i, _i, _vp, _i, _i, _f, _f]),

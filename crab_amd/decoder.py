@@ -698,6 +698,140 @@ class GenerationEngine:
         logits = ops.gemm(hn, self.lm_head.weight, out=logits_out, out_fp32=True)
         return logits, hn
 
+    # ------------------------------------------------------------------ teacher-forced scoring
+    def key_visibility(self, attention_mask, B: int, T: int, width: int):
+        """2-D attention_mask [B, T] over ALL keys (cached + new) -> (kv_start, key_mask) for the attention kernels, at most one of them set:
+        nothing masked -> (None, None); left padding (zeros, then ones: what prepare_multimodal_inputs builds, unified_arch.py:344-348) ->
+        int32 [B] index of the first visible key per sequence (whole key tiles below it are skipped); any other mask (holes anywhere: HF's
+        mask utilities AND the padding mask with the causal one whatever its shape) -> int32 [B, ceil(width / 32)] visibility words
+        (ops.pack_key_mask), `width` >= T bits wide (the cache capacity for the decode shortcut, whose context length travels as a device word).
+        The one classification of a mask: forward() and score() both come here."""
+        if attention_mask is None:
+            return None, None
+        m = attention_mask.to(torch.bool).reshape(B, -1)
+        if m.shape[1] != T:
+            raise ValueError(f"attention_mask covers {m.shape[1]} keys, expected {T} (cached + new tokens)")
+        if bool(m.all()):
+            return None, None
+        start = (~m).sum(1)
+        if bool((m == (torch.arange(T, device=m.device)[None] >= start[:, None])).all()):
+            return start.to(device=self.device, dtype=torch.int32), None
+        full = torch.zeros(B, max(width, T), dtype=torch.bool, device=m.device)
+        full[:, :T] = m
+        return None, ops.pack_key_mask(full).to(self.device)
+
+    def rotary_positions(self, position_ids, B: int, S: int):
+        """position_ids [B | 1, S] -> (contiguous int32 [B, S] on the device, the largest position: the caller grows the RoPE table to cover it)."""
+        p = position_ids.reshape(-1, S)
+        if p.shape[0] not in (1, B):
+            raise ValueError(f"position_ids has {p.shape[0]} rows for a batch of {B}")
+        lo, hi = int(p.min()), int(p.max())
+        if lo < 0:
+            raise ValueError("negative position_ids")
+        return p.expand(B, S).to(device=self.device, dtype=torch.int32).contiguous(), hi
+
+    def _xent_rows(self, h2d: torch.Tensor, row_idx: torch.Tensor, tgt: torch.Tensor, logprob, lse, argmax, r0: int, r1: int, ws):
+        """The fused head over the labelled rows r0 .. r1 of the compacted problem: h2d[row_idx[r]] . lm_head^T against tgt[r]."""
+        ops.lm_head_xent(h2d, self.lm_head.weight, tgt[r0:r1], row_idx=row_idx[r0:r1], logprob=logprob[r0:r1], lse=lse[r0:r1],
+                         argmax=argmax[r0:r1], workspace=ws)
+
+    def xent_from_hidden(self, hn: torch.Tensor, labels) -> "ScoreOutput":
+        """The language-model loss of forward(labels=...) (modeling_llama.py:1261-1274) from the post-final-norm states hn [B, S, D] the logits
+        were made from: shift by one, ignore -100, mean over all labelled tokens of the batch - through crab_lm_head_xent, no second logits pass
+        in PyTorch."""
+        B, S, D = hn.shape
+        row_idx, tgt, seq_off = score_rows(labels, self.lm_head.weight.shape[0], (B, S))
+        n = int(row_idx.shape[0])
+        dev = self.device
+        logprob = torch.empty((n,), device=dev, dtype=torch.float32)
+        lse = torch.empty((n,), device=dev, dtype=torch.float32)
+        argmax = torch.empty((n,), device=dev, dtype=torch.int32)
+        tgt_d, seq_d = tgt.to(dev), seq_off.to(dev)
+        if n:
+            self._xent_rows(hn.reshape(B * S, D), row_idx.to(dev), tgt_d, logprob, lse, argmax, 0, n, None)
+        s, nt, nc, mean = ops.xent_reduce(logprob, tgt_d, argmax, seq_d)
+        return ScoreOutput(mean.reshape(()), s, nt, nc, None)
+
+    def score(self, embeds: torch.Tensor, labels, attention_mask=None, position_ids=None, max_rows: Optional[int] = None,
+              return_token_logprobs: bool = False) -> "ScoreOutput":
+        """Teacher-forced scoring of embeds [B, S, D] against labels [B, S] (HF convention: unshifted, -100 ignored - the target of row t is
+        labels[t + 1], so position 0 never scores): the prefill of forward() (every row through every layer on a scratch bf16 cache, the
+        left-pad mask / position_ids honoured), then crab_lm_head_xent over the LABELLED rows of the final hidden states only.  Sequences are
+        prefilled in chunks (plan_prefill_chunks under the device's memory budget; max_rows caps the rows of a chunk); nothing proportional to
+        rows x vocabulary is allocated.  Returns ScoreOutput(loss = mean NLL over all labelled tokens (NaN when there is none), sum_logprob [B],
+        num_tokens [B], num_correct [B] (argmax == label), token_logprobs = per sequence [n_i] fp32 when asked)."""
+        return self._with_kv_mode("bf16", self._retry_after_eviction, self._score, embeds, labels, attention_mask, position_ids, max_rows,
+                                  return_token_logprobs)
+
+    def _score(self, embeds, labels, attention_mask, position_ids, max_rows, return_token_logprobs):
+        c = self.cfg
+        if embeds.dim() != 3 or embeds.shape[2] != c.hidden_size:
+            raise ValueError(f"embeds must be [B, S, {c.hidden_size}], got {tuple(embeds.shape)}")
+        B, S, D = embeds.shape
+        V = self.lm_head.weight.shape[0]
+        row_idx, tgt, seq_off = score_rows(labels, V, (B, S))
+        if max_rows is not None and int(max_rows) < 1:
+            raise ValueError("max_rows must be positive")
+        if attention_mask is not None and tuple(attention_mask.shape) != (B, S):
+            raise ValueError(f"attention_mask must be [{B}, {S}], got {tuple(attention_mask.shape)}")
+        dev = self.device
+        n = int(row_idx.shape[0])
+        offs = seq_off.tolist()
+        logprob = torch.empty((n,), device=dev, dtype=torch.float32)
+        lse = torch.empty((n,), device=dev, dtype=torch.float32)
+        argmax = torch.empty((n,), device=dev, dtype=torch.int32)
+        tgt_d, seq_d = tgt.to(dev), seq_off.to(dev)
+        if n:
+            embeds = embeds.to(device=dev, dtype=BF16)
+            Tmax = _round_up(S, 64)
+            kv_start, key_mask = self.key_visibility(attention_mask, B, S, S)
+            pos_ids = None
+            if position_ids is not None:
+                pos_ids, hi = self.rotary_positions(position_ids, B, S)
+                self._rope_tab(max(hi + 1, Tmax))
+            Hk, d, L = c.num_key_value_heads, c.head_dim, c.num_hidden_layers
+            Sp = (S + 7) // 8 * 8
+            # chunk rows: the caller's cap, then what the scratch cache + V^T of a chunk may claim of the device next to the activation set
+            per_seq = self.kv_bytes_per_sequence(Tmax) + Hk * d * Sp * 2
+            room = int(0.94 * self.memory_budget(B, Tmax)) - self.fixed_bytes(B, S)
+            cap = min(int(max_rows) if max_rows is not None else 32768, max(1, room // per_seq) * S)
+            chunks = self.plan_prefill_chunks(B, S, max(cap, S))
+            cmax = max(1, min(B, cap // S))
+            if max(chunks) > cmax:                            # below the ring-GEMM regime the planner answers with one chunk: the cap still holds
+                chunks = [cmax] * (B // cmax) + ([B % cmax] if B % cmax else [])
+            cmax = max(chunks)
+            bounds = [0]
+            for n_c in chunks:
+                bounds.append(bounds[-1] + n_c)
+            # chunk-local row indices (row b * S + t of the batch is row (b - b0) * S + t of its chunk), uploaded once
+            local = row_idx.numpy().copy()
+            for b0, b1 in zip(bounds, bounds[1:]):
+                local[offs[b0]:offs[b1]] -= b0 * S
+            local_d = torch.from_numpy(local).to(dev)
+            kv = torch.empty((2, L * cmax * Hk * Tmax * d), device=dev, dtype=BF16)       # rows at or beyond the context are never read
+            vt_buf = torch.empty((cmax * Hk * d * Sp,), device=dev, dtype=BF16)
+            n_max = max(offs[b1] - offs[b0] for b0, b1 in zip(bounds, bounds[1:]))
+            xws = torch.empty((ops.lm_head_xent_bytes(n_max, V),), device=dev, dtype=torch.uint8)
+            for b0, b1 in zip(bounds, bounds[1:]):
+                r0, r1 = offs[b0], offs[b1]
+                if r0 == r1:
+                    continue                                  # no labelled token in these sequences: nothing to prefill
+                n_c = b1 - b0
+                M = n_c * S
+                shape = (L, n_c, Hk, Tmax, d)
+                kc, vc = kv[0][:math.prod(shape)].view(shape), kv[1][:math.prod(shape)].view(shape)
+                vt = vt_buf[:n_c * Hk * d * Sp].view(n_c, Hk, d, Sp)
+                ws = self._workspace(M)
+                ops.cast_rows(embeds[b0:b1].reshape(M, D), ws.x, M, D)
+                _x, hfin = self._layers(ws, n_c, S, kc, vc, 0, Tmax, 0, None, vt,
+                                        pos_ids=pos_ids[b0:b1] if pos_ids is not None else None,
+                                        kv_start=kv_start[b0:b1] if kv_start is not None else None,
+                                        key_mask=key_mask[b0:b1] if key_mask is not None else None)
+                self._xent_rows(hfin, local_d, tgt_d, logprob, lse, argmax, r0, r1, xws)
+        s, nt, nc, mean = ops.xent_reduce(logprob, tgt_d, argmax, seq_d)
+        toks = [logprob[offs[b]:offs[b + 1]] for b in range(B)] if return_token_logprobs else None
+        return ScoreOutput(mean.reshape(()), s, nt, nc, toks)
+
     # ------------------------------------------------------------------ decode
     def _decode_step(self, st: "_DecodeState"):
         """One greedy step entirely on device: embed(cur_ids) -> layers -> norm -> lm_head -> greedy select -> advance."""
@@ -1270,3 +1404,41 @@ class _DecodeState:
 
 def _round_up(a: int, b: int) -> int:
     return (a + b - 1) // b * b
+
+
+class ScoreOutput:
+    """What GenerationEngine.score / UnifiedForCausalLM.score return: `loss` (fp32 scalar: mean NLL over all labelled tokens of the batch, NaN
+    when there is none), `sum_logprob` [B] fp32, `num_tokens` [B] / `num_correct` [B] int32, `token_logprobs` (a list of [n_i] fp32 tensors, or
+    None).  No logits."""
+
+    def __init__(self, loss, sum_logprob, num_tokens, num_correct, token_logprobs=None):
+        self.loss, self.sum_logprob, self.num_tokens, self.num_correct, self.token_logprobs = loss, sum_logprob, num_tokens, num_correct, token_logprobs
+
+
+def score_rows(labels, vocab_size: int, shape=None):
+    """Host-side row selection of teacher-forced scoring.  labels [B, S] (HF convention: unshifted, -100 = ignored) ->
+        row_idx int32 [n]: the flat rows b * S + t whose NEXT token is labelled (labels[b, t + 1] != -100), sequence by sequence, t ascending;
+        tgt     int32 [n]: that label - the already shifted target of row row_idx[i];
+        seq_off int32 [B + 1]: CSR offsets of the sequences over the n compacted rows.
+    Position 0 is never a target and the last row never scores (modeling_llama.py:1265-1266).  A label that is neither -100 nor a token id
+    of the vocabulary raises ValueError (CrossEntropyLoss would index out of range).  CPU tensors; pure host logic."""
+    import numpy as np
+    lab = labels.detach().cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
+    if lab.ndim != 2 or lab.dtype.kind not in "iu":
+        raise ValueError(f"labels must be an integer [B, S] array, got {lab.dtype} {lab.shape}")
+    if shape is not None and tuple(lab.shape) != tuple(shape):
+        raise ValueError(f"labels must be {tuple(shape)} like the embeddings, got {tuple(lab.shape)}")
+    lab = lab.astype(np.int64)
+    B, S = lab.shape
+    bad = (lab != -100) & ((lab < 0) | (lab >= int(vocab_size)))
+    if bad.any():
+        b, t = (int(v[0]) for v in np.nonzero(bad))
+        raise ValueError(f"labels[{b}, {t}] = {int(lab[b, t])}: neither -100 nor a token id below {int(vocab_size)}")
+    nxt = lab[:, 1:]
+    sel = nxt != -100
+    b, t = np.nonzero(sel)                                     # row-major: sequence by sequence, t ascending
+    seq_off = np.zeros(B + 1, dtype=np.int64)
+    np.cumsum(sel.sum(1), out=seq_off[1:])
+    if B * S >= 2 ** 31:
+        raise ValueError("more than 2^31 rows")
+    return (torch.from_numpy((b * S + t).astype(np.int32)), torch.from_numpy(nxt[sel].astype(np.int32)), torch.from_numpy(seq_off.astype(np.int32)))

@@ -653,6 +653,70 @@ def advance(pos_dev, step_dev):
     _lib.check(_lib.load().crab_advance(_lib.ctx(d), _stream(), _p(pos_dev), _p(step_dev)), d)
 
 
+def _chk_i32(name: str, t: Optional[torch.Tensor], n: int, device):
+    # the kernels read these through a raw int32 pointer: an int64 or strided tensor would be misread silently
+    if t is not None and (t.dtype != torch.int32 or t.dim() != 1 or t.shape[0] < n or not t.is_contiguous() or t.device != device):
+        raise ValueError(f"{name} must be a contiguous int32 [{n}] tensor on {device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+
+
+def lm_head_xent_bytes(M: int, N: int) -> int:
+    return int(_lib.load().crab_lm_head_xent_workspace(int(M), int(N)))
+
+
+def lm_head_xent(x: torch.Tensor, w: torch.Tensor, labels: torch.Tensor, row_idx: Optional[torch.Tensor] = None, logprob=None, lse=None,
+                 argmax=None, workspace: Optional[torch.Tensor] = None):
+    """crab_lm_head_xent: the lm_head projection reduced to cross-entropy terms in its epilogue - no logits are stored.
+    x [R, K] bf16 (row stride any multiple of 8), w [N, K] bf16, labels int32 [M] (already shifted; negative = no target, each < N),
+    row_idx int32 [M] or None (row i of the problem is x[row_idx[i]], every index a row of x; None: M = R, the rows of x in order).
+    Returns (logprob [M] fp32 - 0 without a target, lse [M] fp32, argmax [M] int32 - first maximum)."""
+    _chk_bf16(x, w)
+    d = _dev(x)
+    K = x.shape[1]
+    N = w.shape[0]
+    M = labels.shape[0]
+    assert w.shape[1] == K and x.stride(1) == 1 and w.stride(1) == 1
+    _chk_i32("labels", labels, M, x.device)
+    _chk_i32("row_idx", row_idx, M, x.device)
+    if row_idx is None and M != x.shape[0]:
+        raise ValueError(f"labels has {M} entries for {x.shape[0]} rows of x (no row_idx)")
+    if M == 0:
+        raise ValueError("lm_head_xent: no rows")
+    mk = lambda dt: torch.empty((M,), device=x.device, dtype=dt)
+    logprob = mk(torch.float32) if logprob is None else logprob
+    lse = mk(torch.float32) if lse is None else lse
+    argmax = mk(torch.int32) if argmax is None else argmax
+    for nm, t, dt in (("logprob", logprob, torch.float32), ("lse", lse, torch.float32), ("argmax", argmax, torch.int32)):
+        if t.dtype != dt or t.dim() != 1 or t.shape[0] < M or not t.is_contiguous() or t.device != x.device:
+            raise ValueError(f"{nm} must be a contiguous {dt} [{M}] tensor on {x.device}")
+    need = lm_head_xent_bytes(M, N)
+    if workspace is None:
+        workspace = torch.empty((need,), device=x.device, dtype=torch.uint8)
+    _lib.check(_lib.load().crab_lm_head_xent(_lib.ctx(d), _stream(), _p(x), x.stride(0), _p(row_idx), M, _p(w), w.stride(0), N, K, _p(labels),
+                                             _p(logprob), _p(lse), _p(argmax), _p(workspace), workspace.numel() * workspace.element_size()), d)
+    return logprob, lse, argmax
+
+
+def xent_reduce(logprob: torch.Tensor, labels: torch.Tensor, argmax: torch.Tensor, seq_off: torch.Tensor):
+    """crab_xent_reduce over the compacted rows of lm_head_xent: seq_off int32 [B + 1] (CSR) -> (sum_logprob [B] fp32, n_tokens [B] int32,
+    n_correct [B] int32, mean_nll [1] fp32 = the batch's mean over all labelled tokens, NaN when there is none)."""
+    d = _dev(seq_off)
+    B = seq_off.shape[0] - 1
+    dev = seq_off.device
+    _chk_i32("seq_off", seq_off, B + 1, dev)
+    n = logprob.shape[0]
+    _chk_i32("labels", labels, n, dev)
+    _chk_i32("argmax", argmax, n, dev)
+    if logprob.dtype != torch.float32 or not logprob.is_contiguous() or logprob.device != dev:
+        raise ValueError("logprob must be a contiguous float32 tensor on the device of seq_off")
+    s = torch.empty((B,), device=dev, dtype=torch.float32)
+    nt = torch.empty((B,), device=dev, dtype=torch.int32)
+    nc = torch.empty((B,), device=dev, dtype=torch.int32)
+    mean = torch.empty((1,), device=dev, dtype=torch.float32)
+    _lib.check(_lib.load().crab_xent_reduce(_lib.ctx(d), _stream(), _p(logprob), _p(labels), _p(argmax), _p(seq_off), B, _p(s), _p(nt), _p(nc),
+                                            _p(mean)), d)
+    return s, nt, nc, mean
+
+
 def im2col3x3(x: torch.Tensor, B: int, h: int, w: int) -> torch.Tensor:
     """x [B*h*w, C] token-major -> [B*h*w, 9*C] (Conv2d k=3 pad=1 operand)."""
     d = _dev(x)

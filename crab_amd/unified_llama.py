@@ -45,8 +45,8 @@ class UnifiedModel(UnifiedMetaModel, DecoderModel):
 
 
 class CausalLMOutput:
-    def __init__(self, logits, hidden_states=None, past_key_values=None):
-        self.logits, self.hidden_states, self.past_key_values, self.loss = logits, hidden_states, past_key_values, None
+    def __init__(self, logits, hidden_states=None, past_key_values=None, loss=None):
+        self.logits, self.hidden_states, self.past_key_values, self.loss = logits, hidden_states, past_key_values, loss
 
 
 class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
@@ -155,9 +155,12 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
     ):
         """Inference forward (unified_llama.py:47-161): the 1-token decode shortcut (:125-127), the multimodal
         branch (:129-146) and the plain inputs_embeds branch.  Returns an object with `.logits` (fp32, all rows),
-        `.hidden_states` (tuple ending with the post-final-norm states when requested) and `.past_key_values`."""
-        if labels is not None or self.is_avs_task:
-            raise NotImplementedError("training losses / AVS forward are outside the inference hot path")
+        `.hidden_states` (tuple ending with the post-final-norm states when requested) and `.past_key_values`.
+        With `labels` (or, in the multimodal branch, `batch_labels`: the labels prepare_multimodal_inputs splices) `.loss` is the reference's
+        language-model loss (modeling_llama.py:1261-1274: shift by one, -100 ignored, mean over all labelled tokens of the batch, NaN when there
+        is none) as an fp32 scalar, computed by crab_lm_head_xent from the same final hidden states; the logits are what they are without labels."""
+        if self.is_avs_task:
+            raise NotImplementedError("training losses / AVS forward are outside the inference hot path")      # the mask loss of the pixel tasks is training-only
         eng = self._engine
         dev = self.device
         kvd = eng.check_kv_cache_dtype(kwargs.get("kv_cache_dtype") or eng.kv_cache_dtype)
@@ -189,13 +192,16 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
             x, hfin = eng._layers(ws, B, 1, kc, vc, 0, kc.shape[3], 0, pos, None, pos_ids=pos_ids, kv_start=kv_start, key_mask=key_mask)
             hn = hfin.clone()
             logits = ops.gemm(hn, self.lm_head.weight, out_fp32=True)
-            return CausalLMOutput(logits.view(B, 1, -1), (hn.view(B, 1, -1),) if output_hidden_states else None, (kc, vc, n + 1))
+            loss = eng.xent_from_hidden(hn.view(B, 1, -1), labels).loss if labels is not None else None      # one row: no shifted target, NaN
+            return CausalLMOutput(logits.view(B, 1, -1), (hn.view(B, 1, -1),) if output_hidden_states else None, (kc, vc, n + 1), loss)
         if inputs_embeds is None and batch_input_ids is not None:
             # the multimodal branch (unified_llama.py:129-146): mask and positions of the padded batch go to the decoder
             inputs = self.prepare_multimodal_inputs(batch_input_ids=batch_input_ids, batch_labels=batch_labels,
                                                     batch_X_modals=batch_X_modals, batch_task_names=batch_task_names)
             inputs_embeds = inputs['inputs_embeds']
             attention_mask, position_ids = inputs['attention_mask'], inputs['position_ids']
+            if batch_labels is not None:
+                labels = inputs['labels']                      # spliced: -100 over the modality blocks and the left pads (unified_arch.py:293-325)
         elif inputs_embeds is None and input_ids is not None:
             inputs_embeds = self.model.embed_tokens(input_ids)
         inputs_embeds = inputs_embeds.to(device=dev, dtype=BF16)
@@ -208,38 +214,53 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
             eng._rope_tab(self._rope_need)
         kc, vc = eng.alloc_cache(B, Tmax)
         logits, hn = eng.prefill(inputs_embeds, kc, vc, all_logits=True, pos_ids=pos_ids, kv_start=kv_start, key_mask=key_mask)
-        return CausalLMOutput(logits, (hn,) if output_hidden_states else None, (kc, vc, S) if use_cache else None)
+        loss = eng.xent_from_hidden(hn, labels).loss if labels is not None else None
+        return CausalLMOutput(logits, (hn,) if output_hidden_states else None, (kc, vc, S) if use_cache else None, loss)
+
+    @torch.no_grad()
+    def score(self, batch_input_ids=None, batch_labels=None, batch_X_modals=None, batch_task_names=None, inputs_embeds: Optional[torch.Tensor] = None,
+              labels: Optional[torch.LongTensor] = None, attention_mask: Optional[torch.Tensor] = None,
+              position_ids: Optional[torch.LongTensor] = None, return_token_logprobs: bool = False, max_rows: Optional[int] = None):
+        """Teacher-forced scoring - eval loss / perplexity, the log-likelihood of a gold answer, ranking of candidate answers, token accuracy -
+        with the semantics of forward(labels=...) (unified_llama.py:129-160 -> modeling_llama.py:1261-1274) and without logits: the decoder
+        pass of forward() (left-pad mask and position_ids honoured), then the fused lm_head + cross entropy over the labelled rows only
+        (GenerationEngine.score).  Either the four multimodal arguments (labels = the spliced batch_labels) or inputs_embeds [B, S, D] +
+        labels [B, S] (HF convention: unshifted, -100 ignored) with optional attention_mask / position_ids.  Returns an object with
+        .loss (fp32 scalar, mean NLL over all labelled tokens of the batch; NaN when there is none), .sum_logprob [B], .num_tokens [B],
+        .num_correct [B] and, with return_token_logprobs, .token_logprobs (a list of [n_i] fp32 tensors).  max_rows caps the rows of one
+        prefill chunk."""
+        if self.is_avs_task:
+            raise NotImplementedError("training losses / AVS forward are outside the inference hot path")
+        if inputs_embeds is None:
+            if batch_input_ids is None or batch_labels is None:
+                raise ValueError("score() needs batch_input_ids + batch_labels (+ batch_X_modals, batch_task_names) or inputs_embeds + labels")
+            if len(batch_labels) != len(batch_input_ids) or any(tuple(l.shape) != tuple(i.shape) for l, i in zip(batch_labels, batch_input_ids)):
+                raise ValueError("score(): batch_labels must match batch_input_ids sample by sample")
+            inputs = self.prepare_multimodal_inputs(batch_input_ids=batch_input_ids, batch_labels=batch_labels, batch_X_modals=batch_X_modals,
+                                                    batch_task_names=batch_task_names)
+            inputs_embeds, labels = inputs['inputs_embeds'], inputs['labels']
+            attention_mask, position_ids = inputs['attention_mask'], inputs['position_ids']
+        if labels is None:
+            raise ValueError("score() needs labels")
+        if inputs_embeds.dim() != 3 or tuple(labels.shape) != tuple(inputs_embeds.shape[:2]):
+            raise ValueError(f"score(): inputs_embeds [B, S, D] and labels [B, S] expected, got {tuple(inputs_embeds.shape)} and {tuple(labels.shape)}")
+        if attention_mask is not None and tuple(attention_mask.shape) != tuple(labels.shape):
+            raise ValueError(f"score(): attention_mask must be {tuple(labels.shape)}, got {tuple(attention_mask.shape)}")
+        if position_ids is not None and position_ids.numel() not in (labels.shape[1], labels.numel()):
+            raise ValueError(f"score(): position_ids must be [B | 1, S], got {tuple(position_ids.shape)}")
+        return self._engine.score(inputs_embeds, labels, attention_mask=attention_mask, position_ids=position_ids, max_rows=max_rows,
+                                  return_token_logprobs=return_token_logprobs)
 
     def _key_visibility(self, attention_mask, B: int, T: int, width: int):
-        """2-D attention_mask [B, T] over ALL keys (cached + new) -> (kv_start, key_mask) for the attention kernels, at most one of them set:
-        nothing masked -> (None, None); left padding (zeros, then ones: what prepare_multimodal_inputs builds, unified_arch.py:344-348) ->
-        int32 [B] index of the first visible key per sequence (whole key tiles below it are skipped); any other mask (holes anywhere: HF's
-        mask utilities AND the padding mask with the causal one whatever its shape) -> int32 [B, ceil(width / 32)] visibility words
-        (ops.pack_key_mask), `width` >= T bits wide (the cache capacity for the decode shortcut, whose context length travels as a device word)."""
-        if attention_mask is None:
-            return None, None
-        m = attention_mask.to(torch.bool).reshape(B, -1)
-        if m.shape[1] != T:
-            raise ValueError(f"attention_mask covers {m.shape[1]} keys, expected {T} (cached + new tokens)")
-        if bool(m.all()):
-            return None, None
-        start = (~m).sum(1)
-        if bool((m == (torch.arange(T, device=m.device)[None] >= start[:, None])).all()):
-            return start.to(device=self.device, dtype=torch.int32), None
-        full = torch.zeros(B, max(width, T), dtype=torch.bool, device=m.device)
-        full[:, :T] = m
-        return None, ops.pack_key_mask(full).to(self.device)
+        """2-D attention_mask [B, T] over ALL keys (cached + new) -> (kv_start, key_mask) for the attention kernels: GenerationEngine.key_visibility,
+        the one implementation forward() and score() share."""
+        return self._engine.key_visibility(attention_mask, B, T, width)
 
     def _rotary_positions(self, position_ids, B: int, S: int, Tmax: int):
         """position_ids [B | 1, S] -> contiguous int32 [B, S] on the device (the caller grows the RoPE table to cover them)."""
-        p = position_ids.reshape(-1, S)
-        if p.shape[0] not in (1, B):
-            raise ValueError(f"position_ids has {p.shape[0]} rows for a batch of {B}")
-        lo, hi = int(p.min()), int(p.max())
-        if lo < 0:
-            raise ValueError("negative position_ids")
+        p, hi = self._engine.rotary_positions(position_ids, B, S)
         self._rope_need = max(hi + 1, Tmax)
-        return p.expand(B, S).to(device=self.device, dtype=torch.int32).contiguous()
+        return p
 
     # ------------------------------------------------------------------ generate
     @torch.no_grad()

@@ -370,6 +370,34 @@ int crab_sample_select(crab_ctx* ctx, void* stream, const float* logits, int64_t
                        int min_new_tokens, float temperature, int top_k, float top_p, uint64_t seed);
 
 /* ---------------------------------------------------------------------------------------------
+ * Teacher-forced scoring (csrc/xent.hip): the language-model loss of models/modeling_llama.py:1261-1274 as reached from
+ * models/unified_llama.py:129-160 - logits.float(), shift by one, CrossEntropyLoss(ignore_index = -100) - without the logits.
+ *
+ * crab_lm_head_xent: z = x[M, K] . w[N, K]^T (bf16 operands, fp32 MFMA accumulation: the fp32 logits the lm_head GEMM with c_fp32 emits,
+ * never rounded to bf16) is reduced inside the GEMM's epilogue; per row i it writes
+ *     lse[i]     = log sum_v exp(z[i, v])                       (fp32)
+ *     logprob[i] = z[i, labels[i]] - lse[i]                     (0 where labels[i] < 0: no target)
+ *     argmax[i]  = the first maximum of z[i, :]                 (the rule of crab_argmax / crab_greedy_select)
+ * row_idx (int32 [M], may be NULL): row i of the problem is x[row_idx[i]] (row stride ldx) - only the labelled rows of a hidden-state
+ * buffer reach the GEMM; the caller guarantees that every index is a row of x.  labels: int32 [M], ALREADY SHIFTED by the caller (the
+ * target of hidden row t is token t + 1), each < N.  Any M, N >= 1; K % 8 == 0 (CRAB_E_UNSUPPORTED otherwise), ldx / ldw multiples of 8,
+ * x / w / workspace 16-byte aligned.  workspace: crab_lm_head_xent_workspace(M, N) bytes; CRAB_E_WORKSPACE when smaller.  Its layout:
+ * M x ceil(N / 256) records of four fp32 words - (max, sum exp(z - max), best value, best column as int32) of the row over one 256-column
+ * tile - then fp32 [M], the label logits z[i, labels[i]] (defined where labels[i] >= 0): 2 KB per row at N = 32000, against 128 KB of fp32
+ * logits.  Deterministic: no atomics.
+ *
+ * crab_xent_reduce: per-sequence and batch totals over the COMPACTED rows of crab_lm_head_xent.  seq_off: int32 [B + 1] CSR offsets
+ * (sequence b owns rows seq_off[b] .. seq_off[b + 1] - 1).  sum_logprob[b] (fp32), n_tokens[b] (rows with a label >= 0), n_correct[b]
+ * (argmax == label), and mean_nll[0] = - sum_b sum_logprob[b] / sum_b n_tokens[b] - the reference's mean over all labelled tokens of the
+ * batch, NaN when there is none (as CrossEntropyLoss gives).  Fixed reduction order, bit-identical between runs. */
+int64_t crab_lm_head_xent_workspace(int M, int N);
+int crab_lm_head_xent(crab_ctx* ctx, void* stream, const void* x, int64_t ldx, const int32_t* row_idx, int M, const void* w, int64_t ldw,
+                      int N, int K, const int32_t* labels, float* logprob, float* lse, int32_t* argmax, void* workspace,
+                      int64_t workspace_bytes);
+int crab_xent_reduce(crab_ctx* ctx, void* stream, const float* logprob, const int32_t* labels, const int32_t* argmax, const int32_t* seq_off,
+                     int B, float* sum_logprob, int32_t* n_tokens, int32_t* n_correct, float* mean_nll);
+
+/* ---------------------------------------------------------------------------------------------
  * Fused decoder blocks: the launch sequence of ONE LlamaDecoderLayer / Qwen2DecoderLayer with hyper-LoRA
  * adapted projections (models/modeling_llama.py:805-827 = rmsnorm -> self_attn -> residual -> rmsnorm -> mlp -> residual;
  * models/qwen/modeling_qwen2.py:202-317; peft_hyper/tuners/lora.py:338-350) behind one call, so that a C caller runs a
