@@ -40,6 +40,7 @@ class GemmDesc(C.Structure):
         ("r_fp32", C.c_int32),
         ("rope_row_off", C.c_void_p),
         ("norm_w_fp32", C.c_int32),
+        ("B8", C.c_void_p), ("ldb8", C.c_int64), ("b_scale", C.c_void_p),
     ]
 
 
@@ -97,6 +98,7 @@ class LinearGroup(C.Structure):
         ("ldw", C.c_int64), ("ldra", C.c_int64), ("ldb2", C.c_int64),
         ("N", C.c_int32), ("K", C.c_int32), ("nproj", C.c_int32), ("nl", C.c_int32), ("r", C.c_int32), ("tcols", C.c_int32),
         ("ucols", C.c_int32), ("scaling", C.c_float),
+        ("W8", C.c_void_p), ("ldw8", C.c_int64), ("w_scale", C.c_void_p),
     ]
 
 
@@ -140,6 +142,7 @@ SYMBOLS = {
     "crab_sizeof_attn_desc": (_i, []),
     "crab_sizeof_llama_layer": (_i, []),
     "crab_sizeof_llama_io": (_i, []),
+    "crab_sizeof_linear_group": (_i, []),
     "crab_clip_layer": (_i, [_vp, _vp, C.POINTER(ClipLayerW), C.POINTER(EncIO)]),
     "crab_beats_layer": (_i, [_vp, _vp, C.POINTER(BeatsLayerW), C.POINTER(EncIO)]),
     "crab_qformer_layer": (_i, [_vp, _vp, C.POINTER(QformerLayerW), C.POINTER(EncIO)]),
@@ -180,6 +183,7 @@ SYMBOLS = {
     "crab_qkv_rope_split_ids": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i64]),
     "crab_qkv_rope_split_ragged": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "crab_kv_quant_fp8": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _i64, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "crab_weight_quant_fp8": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _i64, _vp]),
     "crab_attn_decode_fp8": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp, _f, _vp]),
     "crab_attn_decode_masked": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp, _f, _vp]),
     "crab_attn_decode_keymask": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp, _f, _vp, _i64]),

@@ -692,6 +692,15 @@ extern "C" int crab_gemm_bf16(crab_ctx* ctx, void* stream, const crab_gemm_desc*
         if (((uintptr_t)d->A2 & 15) || ((uintptr_t)d->B2 & 15)) return crab_fail(ctx, CRAB_E_INVALID, "gemm: A2/B2 alignment");
         if (d->batch > 1) return crab_fail(ctx, CRAB_E_UNSUPPORTED, "gemm: second K segment is not batched");
     }
+    if (d->B8) {
+        // the opt-in FP8 weights: served exactly where gemm_skinny_dma_kernel would have run (its FP8 form, skinny.hip) and refused anywhere
+        // else - never a silent product with the bf16 weights
+        if (!d->b_scale || d->ldb8 < d->K || (d->ldb8 & 15) || ((uintptr_t)d->B8 & 15) || ((uintptr_t)d->b_scale & 3))
+            return crab_fail(ctx, CRAB_E_INVALID, "gemm: B8 needs b_scale, ldb8 >= K and a multiple of 16 (bytes), 16-byte aligned codes");
+        if (d->batch > 1 || d->M > 16 || (d->tune != 0 && d->tune != 9))
+            return crab_fail(ctx, CRAB_E_UNSUPPORTED, "gemm: FP8 weights (B8) are streamed by the M <= 16 kernel only: unbatched, M <= 16, tune 0 "
+                                                      "(or 9: raw sums to the workspace); use the bf16 weights anywhere else");
+    }
     // ---- weight-streaming regime (decode): M <= 256 rows
     //   M <= 16          : LDS-free skinny kernel (skinny.hip), activations replicated per 16 weight rows
     //   16 < M <= 256    : tiled kernel with split-K over blockIdx.y (needs the caller's workspace) so that

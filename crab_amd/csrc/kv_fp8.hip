@@ -19,16 +19,10 @@
 // instruction, round to nearest even, word select for the upper half).  Everything written to memory is a plain vector store.
 #include "common.h"
 #include "crab_internal.h"
-#include <float.h>
-
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
+#include "fp8_common.h"                     // kv8_scale, pack_fp8x4: the row format, shared with the FP8 decoder weights
 
 namespace {
 
-__device__ __forceinline__ float kv8_scale(float amax) {
-    if (amax == 0.f) return 1.0f;
-    return fmaxf(__fdiv_rn(amax, 448.0f), FLT_MIN);
-}
 // max over the 8 lanes (lane ^ 1, ^ 2, ^ 4) / the 16 lanes of a DPP row
 __device__ __forceinline__ float row8_max(float v) {
     v = fmaxf(v, row_xor4(v));
@@ -42,13 +36,6 @@ __device__ __forceinline__ float row8_sum(float v) {
     v += row_xor1(v);
     return v;
 }
-// four fp32 -> one word of four e4m3fn codes (element 0 in the low byte)
-__device__ __forceinline__ uint32_t pack_fp8x4(float a, float b, float c, float d) {
-    int w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
-    w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
-    return (uint32_t)w;
-}
-
 // ---------------------------------------------------------------------------------------------- bf16 block -> fp8 cache
 // One 16-byte load (8 bf16) per lane; LPR = HD / 8 lanes share a row (16 at d = 128: a DPP row, 8 at d = 64: half of one), amax by DPP,
 // 8 codes = one 8-byte store per lane, one scale store per row.  blockIdx.y: 0 = K, 1 = V.  Rows below row_off[b] of a front-padded

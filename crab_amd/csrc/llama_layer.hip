@@ -30,12 +30,18 @@ struct GroupCall {
     bool rope;                               // decode: RoPE + KV append fused behind this (q|k|v) GEMM
     int rope_prefill_S;                      // prefill: rows per sequence; q / k rotate in the projection's epilogue when the library can (crab_gemm_fuses_prefill_rope)
     int* fused_prefill_rope;                 // out: whether it did
+    bool w8;                                 // decode pass: the group's FP8 weights (crab_linear_group.W8) may serve this call
 };
 
 int check_group(crab_ctx* ctx, const crab_linear_group* g, const char* name) {
     if (!g->W || g->N <= 0 || g->K <= 0 || g->ldw < g->K) {
         char msg[128];
         snprintf(msg, sizeof(msg), "llama_layer: group %s needs W, positive N / K and ldw >= K", name);
+        return crab_fail(ctx, CRAB_E_INVALID, msg);
+    }
+    if (g->W8 && (!g->w_scale || g->ldw8 < g->K || (g->ldw8 & 15) || ((uintptr_t)g->W8 & 15))) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "llama_layer: FP8 weights of group %s need w_scale, ldw8 >= K (multiple of 16) and 16-byte aligned codes", name);
         return crab_fail(ctx, CRAB_E_INVALID, msg);
     }
     if (g->RA && (!g->B2 || g->nproj < 1 || g->nl < 1 || g->r < 1 || g->tcols < g->nproj * (g->nl + g->r) || (g->tcols & 15) ||
@@ -54,6 +60,9 @@ int run_group(crab_ctx* ctx, void* stream, const crab_linear_group* g, const cra
     memset(&d, 0, sizeof(d));
     d.A = c.x; d.lda = c.ldx;
     d.B = g->W; d.ldb = g->ldw;
+    // the opt-in FP8 weights: decode pass (one row per sequence, no V^T scratch) at M <= 16 only - the regime of the kernel that streams them;
+    // prefill (its last_rows_only tail included) and larger decode batches compute with W
+    if (g->W8 && c.w8 && M <= 16) { d.B8 = g->W8; d.ldb8 = g->ldw8; d.b_scale = g->w_scale; }
     d.C = c.out; d.ldc = c.ldc;
     d.bias = g->bias;
     d.R = c.residual; d.ldr = c.ldr;
@@ -161,6 +170,7 @@ int run_layer(crab_ctx* ctx, void* stream, const crab_llama_layer* L, crab_llama
     q.x = io->h; q.ldx = io->ldh; q.out = io->qkv; q.ldc = io->ldqkv; q.act = CRAB_ACT_NONE;
     q.u_ready = (io->u_qkv_ready && L->qkv.RA) ? io->u2 : nullptr;
     q.rope = !prefill && !fuse_attn && !fp8;
+    q.w8 = !prefill;
     int fused_rope = 0;
     if (prefill) { q.rope_prefill_S = S; q.fused_prefill_rope = &fused_rope; }
     if ((rc = run_group(ctx, stream, &L->qkv, io, L, M, q, kc, vc))) return rc;
@@ -241,11 +251,13 @@ int run_layer(crab_ctx* ctx, void* stream, const crab_llama_layer* L, crab_llama
     o.x = io->att; o.ldx = io->ldatt; o.out = io->x; o.ldc = io->ldx; o.residual = io->x; o.ldr = io->ldx; o.act = CRAB_ACT_NONE;
     o.norm_w = L->post_attention_norm_w; o.norm_out = io->h; o.ld_norm = io->ldh; o.eps = L->rms_eps;
     if (ahead_gu) { o.route_next = &L->gu; o.route_u = io->u2; }
+    o.w8 = !prefill;
     if ((rc = run_group(ctx, stream, &L->o, io, L, M, o, nullptr, nullptr))) return rc;
     // ---- gate|up with SwiGLU in the epilogue
     GroupCall g{};
     g.x = io->h; g.ldx = io->ldh; g.out = io->act; g.ldc = io->ldact; g.act = CRAB_ACT_SWIGLU_PAIR;
     g.u_ready = ahead_gu ? io->u2 : nullptr;
+    g.w8 = !prefill;
     if ((rc = run_group(ctx, stream, &L->gu, io, L, M, g, nullptr, nullptr))) return rc;
     // ---- down: x += down(act); h = rmsnorm(x) * next_norm_w (+ the next layer's q|k|v router ahead)
     const bool ahead_q = L->next_qkv != nullptr && L->next_qkv->RA != nullptr && M <= CRAB_DECODE_MAX_ROWS;
@@ -253,6 +265,7 @@ int run_layer(crab_ctx* ctx, void* stream, const crab_llama_layer* L, crab_llama
     w.x = io->act; w.ldx = io->ldact; w.out = io->x; w.ldc = io->ldx; w.residual = io->x; w.ldr = io->ldx; w.act = CRAB_ACT_NONE;
     w.norm_w = L->next_norm_w; w.norm_out = io->h; w.ld_norm = io->ldh; w.eps = L->rms_eps;
     if (ahead_q) { w.route_next = L->next_qkv; w.route_u = io->u2; }
+    w.w8 = !prefill;
     if ((rc = run_group(ctx, stream, &L->down, io, L, M, w, nullptr, nullptr))) return rc;
     io->u_qkv_ready = ahead_q ? 1 : 0;
     return CRAB_OK;
@@ -263,6 +276,7 @@ int run_layer(crab_ctx* ctx, void* stream, const crab_llama_layer* L, crab_llama
 extern "C" {
 
 int crab_sizeof_llama_layer(void) { return (int)sizeof(crab_llama_layer); }
+int crab_sizeof_linear_group(void) { return (int)sizeof(crab_linear_group); }
 int crab_sizeof_llama_io(void) { return (int)sizeof(crab_llama_io); }
 
 int crab_llama_layer_prefill(crab_ctx* ctx, void* stream, const crab_llama_layer* layer, crab_llama_io* io, int layer_index) {

@@ -19,6 +19,7 @@
 // lora_route_row_kernel: the same router as ONE row-owning launch, used for 64 < M <= 256 (one row per clip at decode).
 #include "common.h"
 #include "crab_internal.h"
+#include "fp8_common.h"
 #include <stdlib.h>
 
 namespace {
@@ -42,6 +43,8 @@ struct SkinnyP {
     const float* rope_tab; bf16_t* rope_kc; bf16_t* rope_vc; const int* rope_pos_dev;
     int rope_H, rope_Hk, rope_d, rope_Tmax, rope_pos0;
     const int* rope_row_off;                 // ragged decode batch: row m rotates at slot - rope_row_off[m] (crab_gemm_desc.rope_row_off)
+    // gemm_skinny_dma_w8_kernel only: the e4m3fn codes of B (row stride ldb8 bytes) and one fp32 scale per row of B (crab_gemm_desc.B8 / b_scale)
+    const uint8_t* B8; long ldb8; const float* bscale;
 };
 
 constexpr int SK_WAVES = 8;
@@ -365,6 +368,269 @@ __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_dma_kernel(SkinnyP 
             if (p.c_fp32 & CF_C32) reinterpret_cast<float*>(p.C)[(long)m * p.ldc + n + r] = x;
             else reinterpret_cast<bf16_t*>(p.C)[(long)m * p.ldc + n + r] = f2bf(x);
         }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- M <= 16: FP8 weights through LDS
+// gemm_skinny_dma_w8_kernel: gemm_skinny_dma_kernel<1, 4> for weights stored as e4m3fn codes + one fp32 scale per weight row (w8.hip; W8A16:
+// the activations stay bf16).  Same grid (one block per 16 weight rows + the SKX ride-along blocks), same 8 waves splitting K, same
+// wave-private ring of NS 2-KiB slots filled by LDS-DMA in 1-KiB pieces of 8 rows x 128 B - whole cache lines of a row - and read back with
+// the same XOR swizzle.  A slot of codes therefore spans 128 k (a bf16 slot: 64), its fragment reads return 16 codes per lane which are
+// converted to bf16 in registers (exactly: fp8_common.h) and feed four mfma_f32_16x16x32_bf16 against four activation fragments
+// (lane (fr, fg) of read h holds k = k0 + 64 h + 16 fg .. + 15: MFMA 2h takes the low 8, 2h + 1 the high 8; the activation fragments use
+// the same k order, so the sum is the plain dot product).
+//     C[m, n] = act( bscale[n] * sum_k code[n, k] a[m, k]  +  sum_j B2[n, j] A2[m, j]  +  bias[n] ) (+ res_scale * R)
+// The scale belongs to the main segment only: the bf16 K-extension A2 . B2^T (hyper-LoRA) accumulates apart and the SKX blocks ([R;A]
+// rows, bf16, unscaled) run whole bf16 slots, in a ring loop of their own behind the loop over the codes.  K tail: 16-byte pieces past K come from the zero
+// page; K % 16 == 8 leaves 8 foreign bytes in the last piece of a row (ld_codes % 16 == 0 keeps them inside the row), masked after the read.
+// The per-wave partial tiles are reduced through the ring's own storage (every wave has consumed its slots): 64 KiB of LDS per block.
+// Every epilogue is the bf16 kernel's, with the row scale applied to the reduced main sum.
+template <int NS>
+__global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_dma_w8_kernel(SkinnyP p, float* __restrict__ part) {
+    constexpr int SLOTB = 16 * 128;                                     // bytes: 16 weight rows x 128 B
+    __shared__ __attribute__((aligned(16))) uint8_t ring[SK_WAVES][NS][SLOTB];
+    static_assert(NS * SLOTB >= 2 * 64 * 16, "the ring of a wave holds its two partial tiles");
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int fr = lane & 15, fg = lane >> 4;
+    const int nbN = (p.N + 15) / 16;
+    const bool extra = (int)blockIdx.x >= nbN;                          // block-uniform: this block owns a K range of Bx (bf16), not rows of B
+    const int xe = (int)blockIdx.x - nbN;
+    const int Nw = extra ? 16 : p.N;
+    const int n0 = extra ? 0 : (int)blockIdx.x * 16;
+    const bool rope = p.rope_tab != nullptr && !extra;
+    const int r_bpd = rope ? p.rope_d >> 4 : 1;
+    const int r_hh = (int)blockIdx.x / r_bpd, r_j = (int)blockIdx.x % r_bpd;
+    const bool r_qk = rope && r_hh < p.rope_H + p.rope_Hk;
+    const int r_base = r_hh * p.rope_d, r_half = p.rope_d >> 1;
+
+    // slots of this block: extra - the 64-wide bf16 slots [kx0, kx0 + ks) of Bx (the K ranges of the bf16 kernel: the consumer adds the SKX
+    // partials in order); else nk8 128-wide slots of codes, then nk2 64-wide bf16 slots of B2
+    const int nk64 = (p.K + 63) >> 6;
+    const int nk8 = extra ? 0 : (p.K + 127) >> 7;
+    const int nk2 = (p.A2 && !extra) ? (p.K2 + 63) >> 6 : 0;
+    const int kx0 = extra ? (int)((long)nk64 * xe / SKX) : 0;
+    const int ks = extra ? (int)((long)nk64 * (xe + 1) / SKX) - kx0 : nk8 + nk2;
+    const int s_begin = kx0 + (int)((long)ks * wave / SK_WAVES), s_end = kx0 + (int)((long)ks * (wave + 1) / SK_WAVES);
+    const int nst = s_end - s_begin;
+
+    // staging coordinates of the 2 pieces of a slot (bytes): lane l -> row i*8 + (l >> 3), LDS chunk l & 7, source chunk (l & 7) ^ ((row >> 1) & 7)
+    const uint8_t* zero = reinterpret_cast<const uint8_t*>(g_zero_page_sk);
+    long off8[2], offb[2], off2[2];
+    int kc[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int row = i * 8 + (lane >> 3);
+        const int c = (lane & 7) ^ ((row >> 1) & 7);
+        long wrow = min(n0 + row, Nw - 1);                              // clamped: rows >= N are never stored
+        if (r_qk) wrow = r_base + (row >> 3) * r_half + 8 * r_j + (row & 7);
+        kc[i] = c;
+        off8[i] = wrow * p.ldb8 + c * 16;                               // codes: 16 k per chunk
+        offb[i] = (long)(extra ? row : 0) * p.ldbx + c * 8;             // Bx rows (bf16 elements): 8 k per chunk
+        off2[i] = wrow * p.ldb2 + c * 8;
+    }
+    const long xrow1 = (long)min(fr, p.M - 1) * p.lda, xrow2 = (long)min(fr, p.M - 1) * p.lda2;
+    uint8_t* myring = &ring[wave][0][0];
+    const int fofs0 = fr * 128 + ((fg ^ ((fr >> 1) & 7)) << 4);         // bytes: row fr, source chunk fg -> LDS chunk fg ^ ((fr >> 1) & 7)
+    const int fofs1 = fofs0 ^ 64;                                       // source chunk fg + 4
+    // A wave's slots [s_begin, s_end) are first its slots of codes, then its bf16 slots: two ring loops, each with ONE kind of slot - a
+    // fixed number of vector-memory instructions per slot, so a counted vmcnt says when a slot has landed - and no branch on the kind
+    // inside either (a join inside the loop makes the compiler's wait-count pass drain the ring).  Only the wave that owns the K-extension
+    // runs both (its ring drains once in between); the SKX blocks run the second loop alone.
+    const int n8 = min(max(min(s_end, nk8) - s_begin, 0), nst);         // codes: slots s_begin .. s_begin + n8 - 1
+    const int nb = nst - n8, sb_begin = s_begin + n8 - nk8;             // bf16: slots sb_begin .. of B2 (nk8 = 0 in an SKX block: of Bx)
+    f32x4_t acc8 = {0.f, 0.f, 0.f, 0.f}, accb = {0.f, 0.f, 0.f, 0.f};   // codes . a (unscaled) | the bf16 segments
+    {
+        u32x4 xv[NS][4];
+        // slot ST_ of codes into ring slot U_: 2 DMA pieces + 4 activation fragments
+#define SK8_STAGE(ST_, U_)                                                                                \
+        {                                                                                                 \
+            const int k0_ = (ST_) << 7;                                                                   \
+            _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                               \
+                const uint8_t* src_ = p.B8 + off8[i] + k0_;                                               \
+                src_ = (k0_ + kc[i] * 16 < p.K) ? src_ : zero;                                            \
+                __builtin_amdgcn_global_load_lds((sk_gbl_vptr)src_, (sk_lds_vptr)(myring + (U_) * SLOTB + i * 1024), 16, 0, 2);   \
+            }                                                                                             \
+            _Pragma("unroll") for (int h = 0; h < 4; ++h) {                                               \
+                const int k_ = k0_ + (h >> 1) * 64 + fg * 16 + (h & 1) * 8;                               \
+                const int kk_ = k_ < p.K ? k_ : 0;          /* the codes are zero (or masked) there: any finite activation does */   \
+                xv[U_][h] = *reinterpret_cast<const u32x4*>(p.A + xrow1 + kk_);                           \
+            }                                                                                             \
+        }
+#pragma unroll
+        for (int u = 0; u < NS; ++u)
+            if (u < n8) SK8_STAGE(s_begin + u, u)
+        for (int s = 0; s < n8; s += NS) {
+#pragma unroll
+            for (int u = 0; u < NS; ++u) {
+                if (s + u < n8) {
+                    // slot s+u has landed once at most the NS-1 younger slots (6 vector-memory instructions each) are outstanding
+                    if (s + u + NS - 1 < n8) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 1) * 6) : "memory");
+                    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    u32x4 w0 = *reinterpret_cast<const u32x4*>(myring + u * SLOTB + fofs0);
+                    u32x4 w1 = *reinterpret_cast<const u32x4*>(myring + u * SLOTB + fofs1);
+                    // K % 16 == 8: the upper 8 bytes of the row's last 16-byte piece are not codes (always evaluated: no branch)
+                    const int kb = ((s_begin + s + u) << 7) + fg * 16 + 8;
+                    const bool z0 = kb >= p.K, z1 = kb + 64 >= p.K;
+                    w0[2] = z0 ? 0u : w0[2]; w0[3] = z0 ? 0u : w0[3];
+                    w1[2] = z1 ? 0u : w1[2]; w1[3] = z1 ? 0u : w1[3];
+                    union { u32x4 r; bf16x8_t f; } a0, a1, a2, a3, x0, x1, x2, x3;
+                    a0.r = fp8x8_to_bf16x8(w0[0], w0[1]); a1.r = fp8x8_to_bf16x8(w0[2], w0[3]);
+                    a2.r = fp8x8_to_bf16x8(w1[0], w1[1]); a3.r = fp8x8_to_bf16x8(w1[2], w1[3]);
+                    x0.r = xv[u][0]; x1.r = xv[u][1]; x2.r = xv[u][2]; x3.r = xv[u][3];
+                    acc8 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0.f, x0.f, acc8, 0, 0, 0);
+                    acc8 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1.f, x1.f, acc8, 0, 0, 0);
+                    acc8 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2.f, x2.f, acc8, 0, 0, 0);
+                    acc8 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a3.f, x3.f, acc8, 0, 0, 0);
+                    // the fragments are in registers (the MFMAs consumed them): the ring slot may be refilled
+                    asm volatile("" ::: "memory");
+                    if (s + u + NS < n8) SK8_STAGE(s_begin + s + u + NS, u)
+                }
+            }
+        }
+#undef SK8_STAGE
+    }
+    if (nb > 0) {                                                       // wave-uniform
+        // the bf16 slots, exactly as gemm_skinny_dma_kernel runs them: 64 k per slot, 2 DMA pieces + 2 activation fragments
+        const bool s2 = !extra;
+        const int Ks = s2 ? p.K2 : p.K;
+        const bf16_t* zb = reinterpret_cast<const bf16_t*>(zero);
+        const bf16_t* wb0 = s2 ? p.B2 + off2[0] : p.Bx + offb[0];
+        const bf16_t* wb1 = s2 ? p.B2 + off2[1] : p.Bx + offb[1];
+        const bf16_t* xb = s2 ? p.A2 + xrow2 : p.A + xrow1;
+        u32x4 xw[NS][2];
+#define SKB_STAGE(ST_, U_)                                                                                \
+        {                                                                                                 \
+            const int k0_ = (ST_) << 6;                                                                   \
+            const bf16_t* s0_ = (k0_ + kc[0] * 8 < Ks) ? wb0 + k0_ : zb;                                  \
+            const bf16_t* s1_ = (k0_ + kc[1] * 8 < Ks) ? wb1 + k0_ : zb;                                  \
+            __builtin_amdgcn_global_load_lds((sk_gbl_vptr)s0_, (sk_lds_vptr)(myring + (U_) * SLOTB), 16, 0, 2);          \
+            __builtin_amdgcn_global_load_lds((sk_gbl_vptr)s1_, (sk_lds_vptr)(myring + (U_) * SLOTB + 1024), 16, 0, 2);   \
+            _Pragma("unroll") for (int h = 0; h < 2; ++h) {                                               \
+                const int k_ = k0_ + h * 32 + fg * 8;                                                     \
+                const int kk_ = k_ < Ks ? k_ : 0;                                                         \
+                xw[U_][h] = *reinterpret_cast<const u32x4*>(xb + kk_);                                    \
+            }                                                                                             \
+        }
+#pragma unroll
+        for (int u = 0; u < NS; ++u)
+            if (u < nb) SKB_STAGE(sb_begin + u, u)
+        for (int s = 0; s < nb; s += NS) {
+#pragma unroll
+            for (int u = 0; u < NS; ++u) {
+                if (s + u < nb) {
+                    if (s + u + NS - 1 < nb) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 1) * 4) : "memory");
+                    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    union { u32x4 r; bf16x8_t f; } b0, b1, x0, x1;
+                    b0.r = *reinterpret_cast<const u32x4*>(myring + u * SLOTB + fofs0);
+                    b1.r = *reinterpret_cast<const u32x4*>(myring + u * SLOTB + fofs1);
+                    x0.r = xw[u][0]; x1.r = xw[u][1];
+                    accb = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b0.f, x0.f, accb, 0, 0, 0);
+                    accb = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b1.f, x1.f, accb, 0, 0, 0);
+                    asm volatile("" ::: "memory");
+                    if (s + u + NS < nb) SKB_STAGE(sb_begin + s + u + NS, u)
+                }
+            }
+        }
+#undef SKB_STAGE
+    }
+    // partial tiles into this wave's own ring storage (all of its slots are consumed), then the fixed-order reduction over the waves
+    float* myred = reinterpret_cast<float*>(myring);
+    *reinterpret_cast<f32x4_t*>(myred + lane * 4) = acc8;
+    *reinterpret_cast<f32x4_t*>(myred + 256 + lane * 4) = accb;
+    __syncthreads();
+    if (tid >= 64) return;
+    const int l = tid;
+    const int m = l & 15, n = n0 + (l >> 4) * 4;
+    f32x4_t v8 = *reinterpret_cast<const f32x4_t*>(reinterpret_cast<const float*>(&ring[0][0][0]) + l * 4);
+    f32x4_t vb = *reinterpret_cast<const f32x4_t*>(reinterpret_cast<const float*>(&ring[0][0][0]) + 256 + l * 4);
+#pragma unroll
+    for (int w = 1; w < SK_WAVES; ++w) {
+        v8 += *reinterpret_cast<const f32x4_t*>(reinterpret_cast<const float*>(&ring[w][0][0]) + l * 4);
+        vb += *reinterpret_cast<const f32x4_t*>(reinterpret_cast<const float*>(&ring[w][0][0]) + 256 + l * 4);
+    }
+    if (rope) {
+        // every lane of the wave takes part in the partner exchange, rows >= M included
+        const int cg = l >> 4;
+        const int d = p.rope_d, pos = p.rope_pos0 + (p.rope_pos_dev ? p.rope_pos_dev[0] : 0);
+        // local columns cg*4 .. +3 of this block's tile -> column of the packed projection = the weight row they came from (its scale)
+        const int dim = r_qk ? (cg >> 1) * r_half + 8 * r_j + (cg & 1) * 4 : 16 * r_j + cg * 4;
+        const int col = r_base + dim;
+        float x[4], px[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float t = __fmaf_rn(p.bscale[col + r], v8[r], vb[r]);
+            x[r] = bf2f(f2bf(t + (p.bias ? bf2f(p.bias[col + r]) : 0.f)));          // what the projection stores: the rotation reads bf16
+            px[r] = __shfl_xor(x[r], 32, 64);                                       // the lane two column groups away, same row
+        }
+        if (m >= p.M) return;
+        bf16_t* crow = reinterpret_cast<bf16_t*>(p.C) + (long)m * p.ldc + col;
+        const uint32_t raw0 = pack_bf2(x[0], x[1]), raw1 = pack_bf2(x[2], x[3]);
+        if (!r_qk) {                                                 // value head: cache append, the projection row keeps the value
+            const int hk = r_hh - p.rope_H - p.rope_Hk;
+            *reinterpret_cast<u32x2*>(crow) = u32x2{raw0, raw1};
+            *reinterpret_cast<u32x2*>(p.rope_vc + (((long)m * p.rope_Hk + hk) * p.rope_Tmax + pos) * d + dim) = u32x2{raw0, raw1};
+            return;
+        }
+        const int idim = 8 * r_j + (cg & 1) * 4;                     // index of the rotation pair (first-half dim)
+        const int rp = pos - (p.rope_row_off ? p.rope_row_off[m] : 0);   // rotary position (m < M here); the cache slot stays `pos`
+        const float* cs = p.rope_tab + ((long)rp * r_half + idim) * 2;
+        float o[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float c = cs[2 * r], sn = cs[2 * r + 1];
+            o[r] = cg < 2 ? rope_lo(x[r], px[r], c, sn) : rope_hi(px[r], x[r], c, sn);
+        }
+        const u32x2 ow = {pack_bf2(o[0], o[1]), pack_bf2(o[2], o[3])};
+        if (r_hh < p.rope_H) {
+            *reinterpret_cast<u32x2*>(crow) = ow;                    // q rotated in place of the projection row
+        } else {
+            const int hk = r_hh - p.rope_H;
+            *reinterpret_cast<u32x2*>(crow) = u32x2{raw0, raw1};     // the row keeps the un-rotated key like the unfused pair
+            *reinterpret_cast<u32x2*>(p.rope_kc + (((long)m * p.rope_Hk + hk) * p.rope_Tmax + pos) * d + dim) = ow;
+        }
+        return;
+    }
+    if (m >= p.M || n >= Nw) return;
+    if (extra) {                                        // partial router product x . [R;A]^T over this block's K range, fp32 [SKX][16][16]
+        *reinterpret_cast<f32x4_t*>(p.Tx + ((long)xe * 16 + m) * 16 + n) = vb;
+        return;
+    }
+    float v[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] = n + r < p.N ? __fmaf_rn(p.bscale[n + r], v8[r], vb[r]) : 0.f;
+    if (part) {                                         // fp32 act(sum + bias) + res_scale * R (unrounded) for the row-owning reduction
+        float* o = part + (long)m * p.N + n;            // kernel of gemm.hip, slab layout [M][N]; never with the SwiGLU pair epilogue
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            if (n + r >= p.N) break;
+            float x = v[r];
+            if (p.bias) x += bf2f(p.bias[n + r]);
+            x = apply_act(x, p.act);
+            if (p.R) x += p.res_scale * ld_res(p.R, (long)m * p.ldr + n + r, p.c_fp32);
+            o[r] = x;
+        }
+        return;
+    }
+    if (p.act == ACT_SWIGLU_PAIR) {                     // interleaved (gate, up) columns -> two outputs at column n/2
+        float t[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) t[r] = v[r] + (p.bias ? bf2f(p.bias[n + r]) : 0.f);
+        const float o0 = t[0] / (1.0f + __expf(-t[0])) * t[1], o1 = t[2] / (1.0f + __expf(-t[2])) * t[3];
+        const long oc = (long)m * p.ldc + (n >> 1);
+        if (p.c_fp32 & CF_C32) { reinterpret_cast<float*>(p.C)[oc] = o0; reinterpret_cast<float*>(p.C)[oc + 1] = o1; }
+        else { reinterpret_cast<bf16_t*>(p.C)[oc] = f2bf(o0); reinterpret_cast<bf16_t*>(p.C)[oc + 1] = f2bf(o1); }
+        return;
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        if (n + r >= p.N) break;
+        float x = v[r];
+        if (p.bias) x += bf2f(p.bias[n + r]);
+        x = apply_act(x, p.act);
+        if (p.R) x += p.res_scale * ld_res(p.R, (long)m * p.ldr + n + r, p.c_fp32);
+        if (p.c_fp32 & CF_C32) reinterpret_cast<float*>(p.C)[(long)m * p.ldc + n + r] = x;
+        else reinterpret_cast<bf16_t*>(p.C)[(long)m * p.ldc + n + r] = f2bf(x);
     }
 }
 
@@ -698,6 +964,7 @@ int crab_gemm_skinny_launch(crab_ctx* ctx, hipStream_t s, const crab_gemm_desc* 
     p.Bx = nullptr; p.ldbx = 0; p.Tx = nullptr;
     p.rope_tab = nullptr; p.rope_kc = p.rope_vc = nullptr; p.rope_pos_dev = nullptr; p.rope_H = p.rope_Hk = p.rope_d = p.rope_Tmax = p.rope_pos0 = 0;
     p.rope_row_off = nullptr;
+    p.B8 = nullptr; p.ldb8 = 0; p.bscale = nullptr;
     if (crab_skinny_fuses_rope(d)) {
         p.rope_tab = d->rope_tab; p.rope_kc = (bf16_t*)d->rope_k_cache; p.rope_vc = (bf16_t*)d->rope_v_cache; p.rope_pos_dev = d->rope_pos_dev;
         p.rope_H = d->rope_H; p.rope_Hk = d->rope_Hk; p.rope_d = d->rope_d; p.rope_Tmax = d->rope_Tmax; p.rope_pos0 = d->rope_pos0;
@@ -715,9 +982,15 @@ int crab_gemm_skinny_launch(crab_ctx* ctx, hipStream_t s, const crab_gemm_desc* 
             p.Bx = (const bf16_t*)d->lora_RA; p.ldbx = d->lora_ldra; p.Tx = crab_rowfin_T(d);
             extra_blocks = SKX;
         }
+        if (d->B8) {                                    // the opt-in FP8 weights (crab_gemm_desc.B8): same grid, codes through the ring
+            p.B8 = (const uint8_t*)d->B8; p.ldb8 = d->ldb8; p.bscale = d->b_scale;
+            hipLaunchKernelGGL((gemm_skinny_dma_w8_kernel<4>), dim3((d->N + 15) / 16 + extra_blocks), dim3(SK_WAVES * 64), 0, s, p, part);
+            return crab_check_launch(ctx, "gemm_skinny_dma_w8_kernel");
+        }
         hipLaunchKernelGGL((gemm_skinny_dma_kernel<1, 4>), dim3((d->N + 15) / 16 + extra_blocks), dim3(SK_WAVES * 64), 0, s, p, part);
         return crab_check_launch(ctx, "gemm_skinny_dma_kernel");
     }
+    if (d->B8) return crab_fail(ctx, CRAB_E_UNSUPPORTED, "gemm: FP8 weights (B8) need the M <= 16 LDS-DMA kernel (tune 0 / 9, ldb and ldb2 multiples of 8)");
     // NT (weight tiles per block): bigger NT = fewer replicated activation reads but a smaller grid.  d->tune forces it.
     int mt = d->M <= 16 ? 1 : (d->M <= 32 ? 2 : (d->M <= 64 ? 4 : 8));
     int nt = d->tune > 0 ? d->tune : 0;

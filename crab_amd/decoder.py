@@ -31,6 +31,8 @@ BF16 = torch.bfloat16
 import os as _os
 LAST_ROWS_ONLY = _os.environ.get("CRAB_PREFILL_LAST_ROWS", "1") != "0"
 RAGGED_PAD_MAX = 0.06     # a coalesced wave whose batches differ in length is prefilled as ONE padded batch while the padding costs at most this fraction of the prefill rows
+WEIGHT_DTYPES = ("bf16", "fp8_e4m3")       # GenerationEngine(weight_dtype=...): bf16 decoder weights | opt-in FP8 (e4m3fn codes + fp32 row scales) for decode steps of <= 16 rows
+W8_MAX_ROWS = 16                            # rows up to which a decode step streams the FP8 weights (the regime of gemm_skinny_dma_w8_kernel, csrc/skinny.hip)
 KV_CACHE_DTYPES = ("bf16", "fp8_e4m3")     # GenerationEngine(kv_cache_dtype=...): the default bf16 cache | the opt-in FP8 (OCP e4m3fn) cache with fp32 row scales
 NATIVE_LAYERS = True      # False: issue every launch of a layer from Python (A/B runs and the sequencer-equivalence tests)
 
@@ -155,13 +157,21 @@ class _Workspace:
 class GenerationEngine:
     """Prefill + greedy decode over a DecoderModel + lm_head.  Owns KV caches / workspaces (torch allocator)."""
 
-    def __init__(self, model: DecoderModel, lm_head: LMHead, kv_cache_dtype: str = "bf16"):
-        """kv_cache_dtype: "bf16" (default) or "fp8_e4m3" - the opt-in FP8 KV cache of generate() / generate_many() (include/crab_hip.h "FP8 KV
+    def __init__(self, model: DecoderModel, lm_head: LMHead, kv_cache_dtype: str = "bf16", weight_dtype: str = "bf16"):
+        """weight_dtype: "bf16" (default) or "fp8_e4m3" - the opt-in FP8 decoder weights (include/crab_hip.h "FP8 decoder weights"): the DECODE
+        steps of generate() / generate_many() with at most 16 rows stream the four projection groups of every layer as e4m3fn codes with one
+        fp32 scale per output row (PackedLinearGroup.quantize_fp8; activations, adapters and biases stay bf16).  Out of scope, all on the bf16
+        weights: prefill (the first token's logits equal the bf16 mode's bit for bit), decode batches above 16 rows (the 17-128 row
+        register-direct kernel and beyond), lm_head, forward() and score().  Also settable per call: generate(..., weight_dtype=...).
+        kv_cache_dtype: "bf16" (default) or "fp8_e4m3" - the opt-in FP8 KV cache of generate() / generate_many() (include/crab_hip.h "FP8 KV
         cache": e4m3fn codes + one fp32 scale per cached row and KV head; prefill runs in bf16 into a staging block that crab_kv_quant_fp8 moves
         over, decode attends the fp8 rows through crab_attn_decode_fp8).  Also settable per call: generate(..., kv_cache_dtype=...)."""
         self.model, self.lm_head = model, lm_head
         self._stage = None             # fp8 mode: the bf16 staging pair a prefill chunk runs into (flat, grow-only)
         self.kv_cache_dtype = kv_cache_dtype
+        self.weight_dtype = weight_dtype
+        self._w_depth = 0
+        self._w_used = None            # weight dtype the decode states of the call in progress were built for (last_plan["weight_dtype_used"])
         self.cfg = model.config
         self._rope = None
         self._ws = {}
@@ -195,6 +205,25 @@ class GenerationEngine:
     def _fp8(self) -> bool:
         return getattr(self, "_kv_mode", "bf16") == "fp8_e4m3"
 
+    @staticmethod
+    def check_weight_dtype(v) -> str:
+        if v not in WEIGHT_DTYPES:
+            raise ValueError(f"weight_dtype must be one of {' / '.join(repr(k) for k in WEIGHT_DTYPES)}, got {v!r}")
+        return v
+
+    @property
+    def weight_dtype(self) -> str:
+        """The weight mode of the call in progress (a per-call weight_dtype argument overrides the engine's own for that call), else the engine's."""
+        return self._w_mode
+
+    @weight_dtype.setter
+    def weight_dtype(self, v):
+        self._w_mode = self.check_weight_dtype(v)
+
+    def _w8_rows(self, B: int) -> bool:
+        """True when a decode step of B rows streams the FP8 weights under the mode that holds."""
+        return getattr(self, "_w_mode", "bf16") == "fp8_e4m3" and B <= W8_MAX_ROWS
+
     def _with_kv_mode(self, kv_cache_dtype, fn, *a, **k):
         """Run fn under the per-call mode (None: whatever holds - the engine's, or the enclosing call's for the calls generate() makes itself)."""
         if kv_cache_dtype is None:
@@ -204,6 +233,27 @@ class GenerationEngine:
             return fn(*a, **k)
         finally:
             self._kv_mode = saved
+
+    def _with_modes(self, kv_cache_dtype, weight_dtype, fn, *a, **k):
+        """_with_kv_mode for both per-call modes; both values are checked before either is set, so a refused call changes nothing.  The outermost
+        call also stamps last_plan with the weight dtype its decode states ran with ("bf16" when a decode batch exceeded 16 rows)."""
+        if kv_cache_dtype is not None:
+            self.check_kv_cache_dtype(kv_cache_dtype)
+        saved = self._w_mode
+        if weight_dtype is not None:
+            self._w_mode = self.check_weight_dtype(weight_dtype)
+        outer = self._w_depth == 0                  # generate_many / a split generate() call generate() themselves: one verdict for the whole call
+        if outer:
+            self._w_used = None
+        self._w_depth += 1
+        try:
+            res = self._with_kv_mode(kv_cache_dtype, fn, *a, **k)
+            if outer and isinstance(self.last_plan, dict):
+                self.last_plan["weight_dtype_used"] = self._w_used or "bf16"
+            return res
+        finally:
+            self._w_depth -= 1
+            self._w_mode = saved
 
     def _staging(self, n: int, S: int):
         """fp8 mode: the bf16 block [L, n, Hk, round_up(S, 64), d] x 2 one prefill chunk runs into before crab_kv_quant_fp8 moves it into the
@@ -231,6 +281,10 @@ class GenerationEngine:
         self._kv = {}
         self._attn_ws = {}
         self._table = None
+        self._table8 = None
+        for l in self.model.layers:                 # the FP8 forms of the packed weights (weight_dtype = "fp8_e4m3"): rebuilt on the next use
+            for g in l.groups():
+                g.drop_fp8()
 
     def _rope_tab(self, need: int) -> torch.Tensor:
         if self._rope is None or self._rope.shape[0] < need or self._rope.device != self.device:
@@ -446,13 +500,29 @@ class GenerationEngine:
         return self._kv[key]
 
     # ------------------------------------------------------------------ the layer table of the native sequencer
-    def _layer_table(self):
-        """crab_llama_layer[n_layers] (include/crab_hip.h) over the packed groups: borrowed pointers, rebuilt when a buffer moved."""
+    def _quantized(self):
+        """weight_dtype = "fp8_e4m3": (codes, scale) of every packed group, built (or rebuilt after a weight update) OUTSIDE any graph capture -
+        _state() calls this before a decode step can be captured."""
+        return [g.quantize_fp8() for l in self.model.layers for g in l.groups()]
+
+    def _table_fingerprint(self, w8: bool = False):
+        """Everything a layer table bakes in: the weight mode and every pointer (the FP8 codes and scales included)."""
         layers = self.model.layers
         fp = tuple(t.data_ptr() if t is not None else 0 for l in layers for g in l.groups() for t in (g.W, g.RA, g.B2, g.bias)) + \
             tuple(w.data_ptr() for l in layers for w in (l.input_layernorm.weight, l.post_attention_layernorm.weight)) + \
             (self.model.norm.weight.data_ptr(),)
-        hit = getattr(self, "_table", None)
+        if w8:
+            fp += ("fp8_e4m3",) + tuple(t.data_ptr() for pair in self._quantized() for t in pair)
+        return fp
+
+    def _layer_table(self, w8: bool = False):
+        """crab_llama_layer[n_layers] (include/crab_hip.h) over the packed groups: borrowed pointers, rebuilt when a buffer moved.  w8: the
+        table of the FP8-weight decode steps - every group also carries its codes and row scales (crab_linear_group.W8); prefill, forward()
+        and score() always run on the plain table."""
+        layers = self.model.layers
+        fp = self._table_fingerprint(w8)
+        slot_name = "_table8" if w8 else "_table"
+        hit = getattr(self, slot_name, None)
         if hit is not None and hit[0] == fp:
             return hit[1]
         c = self.cfg
@@ -464,6 +534,9 @@ class GenerationEngine:
             if g.RA is not None:
                 dst.RA, dst.ldra, dst.B2, dst.ldb2 = g.RA.data_ptr(), g.RA.stride(0), g.B2.data_ptr(), g.B2.stride(0)
                 dst.nproj, dst.nl, dst.r, dst.tcols, dst.ucols, dst.scaling = len(g.names), g.nl, g.r, g.t_cols, g.u_cols, g.scaling
+            if w8:
+                codes, wsc = g.quantize_fp8()
+                dst.W8, dst.ldw8, dst.w_scale = codes.data_ptr(), codes.stride(0), wsc.data_ptr()
         for i, l in enumerate(layers):
             e = tab[i]
             fill(e.qkv, l.self_attn._qkv); fill(e.o, l.self_attn._o); fill(e.gu, l.mlp._gu); fill(e.down, l.mlp._down)
@@ -474,13 +547,13 @@ class GenerationEngine:
                 e.next_qkv = C.pointer(tab[i + 1].qkv)
             e.H, e.Hk, e.d, e.rms_eps = c.num_attention_heads, c.num_key_value_heads, c.head_dim, c.rms_norm_eps
             e.norm_w_fp32 = 1 if l.post_attention_layernorm.weight.dtype == torch.float32 else 0
-        self._table = (fp, tab)
+        setattr(self, slot_name, (fp, tab))
         return tab
 
     def _layers_native(self, ws: _Workspace, B: int, S: int, kc: torch.Tensor, vc: torch.Tensor, b0: int, Tmax: int, pos0: int,
                        pos_dev: Optional[torch.Tensor], vt: Optional[torch.Tensor], t0: int = 0, row_off: Optional[torch.Tensor] = None,
                        pos_ids: Optional[torch.Tensor] = None, kv_start: Optional[torch.Tensor] = None, last_rows: bool = False,
-                       kv_scales=None):
+                       kv_scales=None, w8: bool = False):
         """The whole stack through ONE C call (crab_llama_layers, csrc/llama_layer.hip): the same launches in the same order as the
         per-launch Python sequence below, which is kept for the runs that time individual kernels (ops.PROFILER)."""
         io = _lib.LlamaIO()
@@ -508,14 +581,14 @@ class GenerationEngine:
         if kv_scales is not None:                                  # the FP8 KV cache (decode): kc / vc hold codes (byte strides), one fp32 scale per row beside them
             ks, vs = kv_scales
             io.kv_fp8, io.k_scale, io.v_scale, io.scale_layer_stride = 1, ks[0, b0].data_ptr(), vs[0, b0].data_ptr(), ks.stride(0)
-        ops.llama_layers(self._layer_table(), len(self.model.layers), io, self.device)
+        ops.llama_layers(self._layer_table(w8), len(self.model.layers), io, self.device)
 
     # ------------------------------------------------------------------ one pass over the layers
     def _layers(self, ws: _Workspace, B: int, S: int, kc: torch.Tensor, vc: torch.Tensor, b0: int, Tmax: int, pos0: int,
                 pos_dev: Optional[torch.Tensor], vt: Optional[torch.Tensor], pos_ids: Optional[torch.Tensor] = None,
                 kv_start: Optional[torch.Tensor] = None, key_mask: Optional[torch.Tensor] = None, t0: int = 0,
-                row_off: Optional[torch.Tensor] = None, last_rows: bool = False, kv_scales=None):
-        """x (ws.x[:B*S]) -> x after all layers.  Prefill when vt is given (S rows per sequence, positions pos0..),
+                row_off: Optional[torch.Tensor] = None, last_rows: bool = False, kv_scales=None, w8: bool = False):
+        """x (ws.x[:B*S]) -> x after all layers.  w8 (decode steps of generate() only, <= 16 rows): the projections stream the FP8 weights.  Prefill when vt is given (S rows per sequence, positions pos0..),
         decode otherwise (S == 1, position read from pos_dev).  kc/vc: [L, Btot, Hk, Tmax, d]; rows b0..b0+B.
         The RAGGED decode batch (generate_many(coalesce=True)): sequences of different prompt lengths are right-aligned in one cache - a
         prefill writes its rows to slots t0 .. t0 + S - 1 (rotary positions still 0 .. S - 1: only the cache pointers move), a decode step
@@ -532,6 +605,8 @@ class GenerationEngine:
         c = self.cfg
         H, Hk, d = c.num_attention_heads, c.num_key_value_heads, c.head_dim
         M = B * S
+        if w8 and (vt is not None or S != 1 or M > W8_MAX_ROWS or pos_ids is not None or kv_start is not None or key_mask is not None):
+            raise NotImplementedError('weight_dtype="fp8_e4m3" serves the decode steps of generate() with at most 16 rows; prefill, forward() and larger batches run on the bf16 weights')
         if kv_scales is not None:
             if vt is not None or S != 1:
                 raise NotImplementedError('kv_cache_dtype="fp8_e4m3": a prefill runs in bf16 into the staging block (GenerationEngine._prefill_chunk), the fp8 cache takes decode steps only')
@@ -560,7 +635,7 @@ class GenerationEngine:
                                                          (pos_ids is None or (pos_ids.dtype == torch.int32 and pos_ids.stride(1) == 1))))
         last_rows = bool(last_rows) and vt is not None and S > 1 and key_mask is None and pos_dev is None
         if NATIVE_LAYERS and not timed and native_ok and contig and (vt is not None or S == 1):
-            self._layers_native(ws, B, S, kc, vc, b0, Tmax, pos0, pos_dev, vt, t0, row_off, pos_ids, kv_start, last_rows, kv_scales)
+            self._layers_native(ws, B, S, kc, vc, b0, Tmax, pos0, pos_dev, vt, t0, row_off, pos_ids, kv_start, last_rows, kv_scales, w8)
             return x, h
         u_qkv = None                                   # router output for the q|k|v group when a producer epilogue made it
         # small batch: the projection leaves its raw row, ONE launch does RoPE + KV append + split-context attention (as csrc/llama_layer.hip)
@@ -576,10 +651,10 @@ class GenerationEngine:
                 self._last_layer_last_rows(ws, layer, B, S, kcl, vcl, lcontig, Tmax, pos0, vt, pos_ids, kv_start, u_qkv)
                 return x, h
             if fuse_attn or kv_scales is not None:
-                a._qkv(h, out=qkv, t_buf=ws.t, u_buf=ws.u, u_ready=u_qkv)
+                a._qkv(h, out=qkv, t_buf=ws.t, u_buf=ws.u, u_ready=u_qkv, fp8=w8)
             elif vt is None and S == 1 and lcontig and not masked:
                 # decode: RoPE + KV append ride on the q|k|v projection (fused into its split-K reduction when it has one)
-                a._qkv(h, out=qkv, t_buf=ws.t, u_buf=ws.u, u_ready=u_qkv, rope=(tab, kcl, vcl, H, Hk, d, Tmax, pos0, pos_dev), rope_row_off=row_off)
+                a._qkv(h, out=qkv, t_buf=ws.t, u_buf=ws.u, u_ready=u_qkv, rope=(tab, kcl, vcl, H, Hk, d, Tmax, pos0, pos_dev), rope_row_off=row_off, fp8=w8)
             elif vt is not None and pos_dev is None and lcontig:
                 # prefill: q and k rotate (and k lands in the cache) in the projection's epilogue when the library says so; the v columns
                 # (cache append + V^T) are then all that is left for the split pass
@@ -592,7 +667,7 @@ class GenerationEngine:
                 else:
                     ops.qkv_rope_split(qkv, tab, kcl, vcl, vt, B, S, H, Hk, d, Tmax, pos0=pos0, pos_dev=pos_dev, pos_ids=pos_ids)
             else:
-                a._qkv(h, out=qkv, t_buf=ws.t, u_buf=ws.u, u_ready=u_qkv)
+                a._qkv(h, out=qkv, t_buf=ws.t, u_buf=ws.u, u_ready=u_qkv, fp8=w8)
                 ops.qkv_rope_split(qkv, tab, kcl, vcl, vt, B, S, H, Hk, d, Tmax, pos0=pos0, pos_dev=pos_dev, pos_ids=pos_ids, row_off=row_off)
             if vt is not None:
                 Sp = vt.shape[-1]
@@ -611,15 +686,15 @@ class GenerationEngine:
             # (decode regime) the row-owning epilogue that produces h also evaluates the router of the group that consumes h
             ahead_gu = m._gu.routes_ahead(M)
             a._o(att, residual=x, out=x, t_buf=ws.t, u_buf=ws.u, post_norm=(layer.post_attention_layernorm.weight, c.rms_norm_eps, h),
-                 route_next=(m._gu, ws.u2) if ahead_gu else None)
-            m._gu(h, out=act, t_buf=ws.t, u_buf=ws.u, act="swiglu_pair", u_ready=ws.u2 if ahead_gu else None)   # silu(gate(h)) * up(h)
+                 route_next=(m._gu, ws.u2) if ahead_gu else None, fp8=w8)
+            m._gu(h, out=act, t_buf=ws.t, u_buf=ws.u, act="swiglu_pair", u_ready=ws.u2 if ahead_gu else None, fp8=w8)   # silu(gate(h)) * up(h)
             # x += down(act); h = rmsnorm(x) * (next layer's input_layernorm | the final model.norm)
             last = li + 1 == len(layers)
             nxt = self.model.norm.weight if last else layers[li + 1].input_layernorm.weight
             nq = None if last else layers[li + 1].self_attn._qkv
             ahead_q = nq is not None and nq.routes_ahead(M)
             m._down(act, residual=x, out=x, t_buf=ws.t, u_buf=ws.u, post_norm=(nxt, c.rms_norm_eps, h),
-                    route_next=(nq, ws.u2) if ahead_q else None)
+                    route_next=(nq, ws.u2) if ahead_q else None, fp8=w8)
             u_qkv = ws.u2 if ahead_q else None
         return x, h
 
@@ -840,7 +915,7 @@ class GenerationEngine:
         ws = st.ws
         ops.embedding(st.cur_ids, self.model.embed_tokens.weight, out=ws.x[:B])
         x, hfin = self._layers(ws, B, 1, st.kc, st.vc, 0, st.Tmax, 0, st.pos_dev, None, row_off=st.row_off,
-                               kv_scales=(st.ks, st.vs) if st.ks is not None else None)
+                               kv_scales=(st.ks, st.vs) if st.ks is not None else None, w8=st.w8)
         ops.gemm(hfin, self.lm_head.weight, out=st.logits)
         if st.want_hidden:
             ops.copy_rows(hfin, st.hn, B, hfin.shape[1])
@@ -880,17 +955,22 @@ class GenerationEngine:
         pad = int(pad_token_id) if pad_token_id is not None else (eos if eos >= 0 else 0)
         ws = self._workspace(B, slot, decode=True)
         tab = self._rope_tab(Tmax)
+        # the weight mode of this state's decode steps; the FP8 forms are (re)built here, before any capture, and their pointers enter the key
+        w8 = self._w8_rows(B)
+        w8_key = ("fp8_e4m3",) + tuple(t.data_ptr() for pair in self._quantized() for t in pair) if w8 else ("bf16",)
+        self._w_used = "bf16" if (not w8 or self._w_used == "bf16") else "fp8_e4m3"
         key = (B, Tmax, max_new_tokens, eos, pad, int(min_new_tokens), bool(return_hidden), kc.data_ptr(), vc.data_ptr(), id(ws),
                tab.data_ptr(), self.lm_head.weight.data_ptr(), self.model.embed_tokens.weight.data_ptr(),
                self.model.layers[0].self_attn._qkv.W.data_ptr(),
                self.model.layers[0].self_attn._qkv.RA is not None, sampling, bool(ragged),
-               self._kv_mode, ks.data_ptr() if ks is not None else 0, vs.data_ptr() if vs is not None else 0)
+               self._kv_mode, ks.data_ptr() if ks is not None else 0, vs.data_ptr() if vs is not None else 0, w8_key)
         st = self._dec.get(slot)
         if st is None or st.key != key:
             st = _DecodeState()
             st.key, st.graph = key, None
             st.B, st.Tmax, st.kc, st.vc, st.slot, st.ws = B, Tmax, kc, vc, slot, ws
             st.ks, st.vs = ks, vs
+            st.w8 = w8
             st.logits = torch.empty((B, V), device=dev, dtype=torch.float32)
             st.hn = torch.empty((B, D), device=dev, dtype=BF16)
             st.cur_ids = torch.empty((B,), device=dev, dtype=torch.int64)
@@ -1033,9 +1113,9 @@ class GenerationEngine:
     def generate(self, embeds: torch.Tensor, max_new_tokens: int, eos_token_id: Optional[int] = None,
                  pad_token_id: Optional[int] = None, min_new_tokens: int = 0, prefill_chunk: int = 0, use_graph: bool = True,
                  return_step_logits: bool = False, return_hidden: bool = False, decode_streams: int = 1,
-                 return_first_logits: bool = False, sampling=None, kv_cache_dtype: Optional[str] = None):
-        """kv_cache_dtype: "bf16" / "fp8_e4m3" for this call (None: the engine's); see _generate for the rest."""
-        return self._with_kv_mode(kv_cache_dtype, self._retry_after_eviction, self._generate, embeds, max_new_tokens, eos_token_id, pad_token_id,
+                 return_first_logits: bool = False, sampling=None, kv_cache_dtype: Optional[str] = None, weight_dtype: Optional[str] = None):
+        """kv_cache_dtype / weight_dtype: "bf16" / "fp8_e4m3" for this call (None: the engine's); see _generate for the rest."""
+        return self._with_modes(kv_cache_dtype, weight_dtype, self._retry_after_eviction, self._generate, embeds, max_new_tokens, eos_token_id, pad_token_id,
                                   min_new_tokens, prefill_chunk, use_graph, return_step_logits, return_hidden, decode_streams, return_first_logits, sampling)
 
     def _generate(self, embeds: torch.Tensor, max_new_tokens: int, eos_token_id: Optional[int] = None,
@@ -1147,9 +1227,10 @@ class GenerationEngine:
     def generate_many(self, embeds_list: List[torch.Tensor], max_new_tokens: int, eos_token_id: Optional[int] = None,
                       pad_token_id: Optional[int] = None, min_new_tokens: int = 0, use_graph: bool = True, sampling=None,
                       return_first_logits: bool = False, coalesce: bool = False, max_rows: Optional[int] = None,
-                      return_step_logits: bool = False, return_hidden: bool = False, kv_cache_dtype: Optional[str] = None):
-        """kv_cache_dtype: "bf16" / "fp8_e4m3" for this call (None: the engine's); see _generate_many for the rest."""
-        return self._with_kv_mode(kv_cache_dtype, self._retry_after_eviction, self._generate_many, embeds_list, max_new_tokens, eos_token_id, pad_token_id,
+                      return_step_logits: bool = False, return_hidden: bool = False, kv_cache_dtype: Optional[str] = None,
+                      weight_dtype: Optional[str] = None):
+        """kv_cache_dtype / weight_dtype: "bf16" / "fp8_e4m3" for this call (None: the engine's); see _generate_many for the rest."""
+        return self._with_modes(kv_cache_dtype, weight_dtype, self._retry_after_eviction, self._generate_many, embeds_list, max_new_tokens, eos_token_id, pad_token_id,
                                   min_new_tokens, use_graph, sampling, return_first_logits, coalesce, max_rows, return_step_logits, return_hidden)
 
     def _generate_many(self, embeds_list: List[torch.Tensor], max_new_tokens: int, eos_token_id: Optional[int] = None,

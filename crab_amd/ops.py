@@ -192,8 +192,11 @@ def gemm(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, 
          residual: Optional[torch.Tensor] = None, res_scale: float = 1.0, x2: Optional[torch.Tensor] = None,
          w2: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, out_fp32: bool = False, tune: int = 0,
          post_norm=None, rope=None, route=None, lora_self=None, info: Optional[dict] = None, prof_class: Optional[str] = None,
-         rope_row_off: Optional[torch.Tensor] = None) -> torch.Tensor:
+         rope_row_off: Optional[torch.Tensor] = None, w8=None) -> torch.Tensor:
     """out[M,N] = res_scale*residual + act(x[M,K] @ w[N,K]^T + x2 @ w2^T + bias).  2-D row-strided operands.
+    w8 = (codes uint8 [N, K], scale fp32 [N]) (weight_quant_fp8 of w; M <= 16 only): the opt-in FP8 weights - the product is
+    scale[n] * sum_k float(codes[n, k]) x[m, k], streamed by gemm_skinny_dma_w8_kernel; w2 / bias / lora_self stay bf16.  The library refuses
+    the call (CrabHipError) wherever that kernel would not run; it never falls back to w.
     rope = (tab, k_cache, v_cache, H, Hk, d, Tmax, pos0, pos_dev): packed q|k|v projection of ONE row per sequence followed
     by RoPE + KV-cache append (== qkv_rope_split(B=M, S=1) on out), fused into the split-K reduction when there is one.
     rope = (..., pos_dev = None, S, pos_ids[, vt]): the PREFILL form, S rows per sequence - when the library says so (info["fused_prefill_rope"]
@@ -274,6 +277,12 @@ def gemm(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, 
                 g.rope_vt, g.rope_vt_ld = rope[11].data_ptr(), rope[11].stride(-2)
             if info is not None:                                   # 0: not fused; 1: q / k; 2: q / k / v (no split pass left)
                 info["fused_prefill_rope"] = int(_lib.load().crab_gemm_fuses_prefill_rope(C.byref(g)))
+    if w8 is not None:
+        codes, wsc = w8
+        if codes.dtype != torch.uint8 or wsc.dtype != torch.float32 or tuple(codes.shape) != (N, K) or codes.stride(1) != 1 or wsc.numel() != N or \
+                not wsc.is_contiguous() or codes.device != x.device or wsc.device != x.device:
+            raise ValueError("w8 = (codes uint8 [N, K], scale fp32 [N]) on the device of x, as weight_quant_fp8 returns them")
+        g.B8, g.ldb8, g.b_scale = codes.data_ptr(), codes.stride(0), wsc.data_ptr()
     if M <= DECODE_MAX_ROWS:
         ws = _splitk_workspace(x.device)
         g.workspace, g.workspace_bytes = ws.data_ptr(), ws.numel()
@@ -527,6 +536,26 @@ def kv_quant_fp8(k_src, v_src, k_codes, v_codes, k_scale, v_scale, b0: int = 0, 
     _lib.check(_lib.load().crab_kv_quant_fp8(_lib.ctx(d), _stream(), _p(k_src), _p(v_src), k_src.stride(0), Tsrc, t0, _p(k_codes), _p(v_codes),
                                              k_codes.stride(0), _p(k_scale), _p(v_scale), k_scale.stride(0), L, Bc, Hk, hd, Tmax, b0, t_dst, S,
                                              _p(row_off)), d)
+
+
+def weight_quant_fp8(w: torch.Tensor, codes: Optional[torch.Tensor] = None, scale: Optional[torch.Tensor] = None):
+    """crab_weight_quant_fp8: w [N, K] bf16 (row stride a multiple of 8) -> (codes uint8 [N, K], scale fp32 [N]): OCP e4m3fn with one scale per
+    row, scale = amax / 448 (1.0 for an all-zero row, floored at FLT_MIN), code = e4m3fn_rne(w * (1 / scale)) - tests/w8_ref.py states it in
+    torch.  codes may be a view with a row stride > K (a multiple of 16 bytes); fresh ones are allocated with K rounded up to 16."""
+    _chk_bf16(w)
+    d = _dev(w)
+    N, K = w.shape
+    if w.stride(1) != 1:
+        raise ValueError("weight_quant_fp8: rows of w must be contiguous")
+    if codes is None:
+        codes = torch.empty((N, (K + 15) // 16 * 16), device=w.device, dtype=torch.uint8)[:, :K]
+    if scale is None:
+        scale = torch.empty((N,), device=w.device, dtype=torch.float32)
+    if codes.dtype != torch.uint8 or tuple(codes.shape) != (N, K) or codes.stride(1) != 1 or scale.dtype != torch.float32 or scale.numel() != N or \
+            not scale.is_contiguous():
+        raise ValueError("weight_quant_fp8: codes uint8 [N, K] (contiguous rows) and scale fp32 [N] expected")
+    _lib.check(_lib.load().crab_weight_quant_fp8(_lib.ctx(d), _stream(), _p(w), w.stride(0), N, K, _p(codes), codes.stride(0), _p(scale)), d)
+    return codes, scale
 
 
 def attn_decode_fp8(qkv, rope_tab, k_codes, v_codes, k_scale, v_scale, o, B, H, Hk, head_dim, Tmax, pos0, scale, pos_dev=None, kv_start=None):

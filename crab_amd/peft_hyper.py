@@ -117,6 +117,7 @@ class PackedLinearGroup:
         self.r = self.nl = 0
         self.scaling = 1.0
         self.RA = self.B2 = None
+        self._w8 = None                   # quantize_fp8(): (W.data_ptr(), W._version, codes, scale)
         self.linears = [Linear(self, i) for i in range(len(names))]
 
     def row_range(self, i: int):
@@ -141,6 +142,21 @@ class PackedLinearGroup:
         for lin in self.linears:
             lin._attach_lora()
 
+    def quantize_fp8(self):
+        """(codes uint8 [N, K], scale fp32 [N]): the opt-in FP8 form of W (ops.weight_quant_fp8: OCP e4m3fn, one scale per packed row as
+        stored - the interleaved gate|up rows each get their own).  Built on first use and kept until W moves (data pointer) or is written
+        in place (load_state_dict / copy_ through the member Parameters bump W._version); rebind() and GenerationEngine.invalidate() drop it.
+        W itself stays: prefill, decode batches above 16 rows, forward() and score() compute with it."""
+        hit = self._w8
+        if hit is not None and hit[0] == self.W.data_ptr() and hit[1] == self.W._version:
+            return hit[2], hit[3]
+        codes, scale = ops.weight_quant_fp8(self.W)
+        self._w8 = (self.W.data_ptr(), self.W._version, codes, scale)
+        return codes, scale
+
+    def drop_fp8(self):
+        self._w8 = None
+
     def rebind(self, fn=None):
         """Re-point the member Parameters at the packed buffers, after applying `fn` (the tensor map of nn.Module._apply:
         a device move) to the buffers.  nn.Module._apply replaces every view Parameter with an independent tensor, which
@@ -154,6 +170,7 @@ class PackedLinearGroup:
                 raise TypeError("crab_amd keeps decoder weights in bfloat16: .float() / .half() / .to(dtype) are not supported")
             return r
         self.W, self.bias, self.RA, self.B2 = mv(self.W), mv(self.bias), mv(self.RA), mv(self.B2)
+        self._w8 = None
         for i, lin in enumerate(self.linears):
             lin.weight = nn.Parameter(self.rows(self.W, i), requires_grad=False)
             if self.bias is not None:
@@ -163,11 +180,13 @@ class PackedLinearGroup:
 
     def __call__(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
                  t_buf: Optional[torch.Tensor] = None, u_buf: Optional[torch.Tensor] = None, post_norm=None, act: str = "none", rope=None, route_next=None, u_ready=None, info=None,
-                 rope_row_off=None) -> torch.Tensor:
-        """y = group(x) (+residual).  post_norm = (rms_weight, eps, h_out): additionally h_out = rmsnorm(y) * rms_weight
+                 rope_row_off=None, fp8: bool = False) -> torch.Tensor:
+        """y = group(x) (+residual).  fp8: the caller (GenerationEngine, weight_dtype = "fp8_e4m3", decode steps) asks for the FP8 weights;
+        they serve M <= 16 only, W serves everything else.  post_norm = (rms_weight, eps, h_out): additionally h_out = rmsnorm(y) * rms_weight
         (the LlamaRMSNorm that follows o_proj / down_proj), fused into the GEMM epilogue in the decode regime.
         act = "swiglu_pair" (interleaved groups): returns silu(member0(x)) * member1(x), [M, N/2]."""
         M = x.shape[0]
+        w8 = self.quantize_fp8() if (fp8 and M <= 16) else None
         if act == "swiglu_pair" and not self.interleave:
             raise ValueError("swiglu_pair needs an interleaved group")
         # route_next = (group, u_out): this GEMM's fused post-norm also evaluates the router of the NEXT group on the
@@ -178,13 +197,13 @@ class PackedLinearGroup:
             route = (ng.RA, len(ng.names), ng.nl, ng.r, ng.u_cols, ng.scaling, nu[:M, :ng.u_cols])
         if self.RA is None:
             return ops.gemm(x, self.W, bias=self.bias, residual=residual, out=out, post_norm=post_norm, act=act, rope=rope, route=route, info=info,
-                            prof_class=self.prof_class, rope_row_off=rope_row_off)
+                            prof_class=self.prof_class, rope_row_off=rope_row_off, w8=w8)
         if u_ready is None and M <= 16 and post_norm is not None and len(self.names) == 1 and ops.ROWFIN and ops.rowfin_lora_ok(self.nl, self.r, self.N):
             # the reference's batch sizes (M <= 16), o_proj / down_proj: no router launches - the [R;A] rows ride on the projection's
             # launch and the update is applied by the wide layer tail (csrc/rowfin.hip) together with the residual row, its RMSNorm and
             # the next group's router
             return ops.gemm(x, self.W, bias=self.bias, residual=residual, out=out, post_norm=post_norm, act=act, route=route,
-                            lora_self=(self.RA, self.nl, self.r, self.scaling, self.B2), prof_class=self.prof_class)
+                            lora_self=(self.RA, self.nl, self.r, self.scaling, self.B2), prof_class=self.prof_class, w8=w8)
         if u_ready is not None:
             u = u_ready[:M, :self.u_cols]
         else:
@@ -192,7 +211,7 @@ class PackedLinearGroup:
             # route logits | lora_A(x) -> softmax mix, K split over blocks (skinny.hip); t_buf is the partial-sum workspace
             ops.hyperlora_route(x, self.RA, len(self.names), self.nl, self.r, self.u_cols, self.scaling, out=u, workspace=t_buf)
         return ops.gemm(x, self.W, bias=self.bias, residual=residual, x2=u, w2=self.B2, out=out, post_norm=post_norm, act=act, rope=rope,
-                        route=route, info=info, prof_class=self.prof_class, rope_row_off=rope_row_off)
+                        route=route, info=info, prof_class=self.prof_class, rope_row_off=rope_row_off, w8=w8)
 
     def routes_ahead(self, M: int) -> bool:
         """True when a producer GEMM may evaluate this group's router in its fused post-norm epilogue (decode regime)."""

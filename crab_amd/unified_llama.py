@@ -59,7 +59,8 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
         self.vocab_size = config.vocab_size
         self.lm_head = LMHead(config.hidden_size, config.vocab_size, device)
         self.is_avs_task = False
-        self._engine = GenerationEngine(self.model, self.lm_head, kv_cache_dtype=kwargs.get("kv_cache_dtype", "bf16"))   # "fp8_e4m3": the opt-in FP8 KV cache
+        self._engine = GenerationEngine(self.model, self.lm_head, kv_cache_dtype=kwargs.get("kv_cache_dtype", "bf16"),   # "fp8_e4m3": the opt-in FP8 KV cache
+                                        weight_dtype=kwargs.get("weight_dtype", "bf16"))                                # "fp8_e4m3": the opt-in FP8 decoder weights (decode steps of <= 16 rows)
         self._past = None
 
     # ------------------------------------------------------------------ plumbing
@@ -268,6 +269,8 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
         """unified_llama.py:244-267.  kwargs understood (HF names): max_new_tokens, min_new_tokens, eos_token_id,
         pad_token_id, use_cache, do_sample (+ temperature, top_k, top_p, seed), output_logits / return_dict_in_generate (parity audits),
         kv_cache_dtype ("bf16" | "fp8_e4m3": the KV cache of this call, default the engine's - GenerationEngine(kv_cache_dtype=...)),
+        weight_dtype ("bf16" | "fp8_e4m3": the decoder weights the decode steps of this call stream, default the engine's; FP8 serves decode
+        batches of at most 16 rows - prefill, larger batches, lm_head, forward() and score() stay on the bf16 weights),
         output_first_logits (ids + the fp32 logits of the first generated position, [B, V]: the record the multi-GPU eval gathers),
         inputs_embeds (skip prepare_multimodal_inputs)."""
         self._check_generate_kwargs(kwargs)
@@ -290,7 +293,7 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
                                     min_new_tokens=int(kwargs.get("min_new_tokens", 0) or 0),
                                     prefill_chunk=int(kwargs.get("prefill_chunk", 0)), use_graph=kwargs.get("use_graph", True),
                                     return_step_logits=want_logits, decode_streams=int(kwargs.get("decode_streams", 1)),
-                                    return_first_logits=want_first, sampling=sampling, kv_cache_dtype=kwargs.get("kv_cache_dtype"))
+                                    return_first_logits=want_first, sampling=sampling, kv_cache_dtype=kwargs.get("kv_cache_dtype"), weight_dtype=kwargs.get("weight_dtype"))
         if want_logits or want_first:
             res = list(res)
             out = type("GenerateOutput", (), {})()
@@ -337,7 +340,7 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
         return self._engine.generate_many(embeds, int(kwargs.get("max_new_tokens", 20)), eos_token_id=eos, pad_token_id=pad,
                                           min_new_tokens=int(kwargs.get("min_new_tokens", 0) or 0), use_graph=kwargs.get("use_graph", True),
                                           sampling=sampling, return_first_logits=want_first, coalesce=coalesce, max_rows=max_rows,
-                                          kv_cache_dtype=kwargs.get("kv_cache_dtype"))
+                                          kv_cache_dtype=kwargs.get("kv_cache_dtype"), weight_dtype=kwargs.get("weight_dtype"))
 
     # HF generate() arguments that would CHANGE what is decoded and that this path does not implement: refused by name instead of ignored
     # (name -> the value that means "off").  Everything the reference's loops pass (use_cache, max_new_tokens; do_sample & co. from the
@@ -447,7 +450,7 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
         outs = self._engine.generate_many(embeds, int(kwargs.get("max_new_tokens", 20)), eos_token_id=eos, pad_token_id=pad,
                                           min_new_tokens=int(kwargs.get("min_new_tokens", 0) or 0), use_graph=kwargs.get("use_graph", True),
                                           sampling=sampling, coalesce=True, max_rows=max_rows, return_hidden=True,
-                                          kv_cache_dtype=kwargs.get("kv_cache_dtype"))
+                                          kv_cache_dtype=kwargs.get("kv_cache_dtype"), weight_dtype=kwargs.get("weight_dtype"))
         return inputs, outs
 
     def _avs_segment(self, samples, inputs, outs, chosen):

@@ -133,6 +133,12 @@ typedef struct {
     /* norm_w is fp32 [N] (16-byte aligned) instead of bf16 (ABI 9): the RMSNorm weight is not a matrix operand; kept in fp32 it removes a
      * 2^-9 relative error from every channel of every normalised row.  With the fp32 residual stream only (c_fp32 = r_fp32 = 1). */
     int32_t norm_w_fp32;
+    /* optional FP8 form of B (additions under ABI 13, see "FP8 decoder weights" below): B8 [N, K] e4m3fn codes (row stride ldb8 BYTES, a multiple
+     * of 16; 16-byte aligned) and b_scale fp32 [N], as crab_weight_quant_fp8 writes them.  B stays required and holds the bf16 weights of the same
+     * matrix.  With B8 set the product is  b_scale[n] * sum_k float(B8[n,k]) A[m,k]  (fp32; A stays bf16, the codes become bf16 exactly in
+     * registers) and the call is served by the M <= 16 weight-streaming kernel only: unbatched, M <= 16, tune 0 (or 9).  Anywhere else it returns
+     * CRAB_E_UNSUPPORTED - never a silent product with the bf16 weights.  B2 / lora_RA / bias stay bf16 and unscaled.  NULL: bf16 weights. */
+    const void* B8; int64_t ldb8; const float* b_scale;
 } crab_gemm_desc;
 
 /* Rows up to which crab_gemm_bf16 treats a problem as WEIGHT-STREAMING (the decode regime: one row per clip) when a workspace is given:
@@ -313,6 +319,18 @@ int crab_attn_decode_fp8(crab_ctx* ctx, void* stream, const void* qkv, int64_t l
                          void* v_codes, float* k_scale, float* v_scale, void* o, int64_t ldo, int B, int H, int Hk, int d, int Tmax,
                          int pos0, const int32_t* pos_dev, float scale, const int32_t* kv_start);
 
+/* ---------------------------------------------------------------------------------------------
+ * FP8 decoder weights (opt-in, additions under ABI 13; no reference counterpart: the reference computes with bf16 / fp32 weights).  At the
+ * reference's batch sizes (1 clip per generate(), 8 in the eval loop) a decode step is a stream of the projection weights; this mode halves
+ * its bytes.  W [N, K] bf16 -> codes [N, K] uint8 (OCP e4m3fn) + scale fp32 [N], ONE scale per output row, by the row formula of the FP8 KV
+ * cache above (scale = amax / 448; 1.0 for an all-zero row; floored at FLT_MIN; code = e4m3fn_rne(w * (1 / scale))).  Rows are quantised as
+ * stored: the interleaved gate|up rows of a packed group each get their own scale.
+ * crab_weight_quant_fp8: one launch; K % 8 == 0, ldw % 8 == 0, W and codes 16-byte aligned, ld_codes (bytes) % 16 == 0 and >= K (refused
+ * otherwise).  Bytes K .. ld_codes - 1 of a code row are left as they are.
+ * Consumers: crab_gemm_desc.B8 / ldb8 / b_scale and crab_linear_group.W8 / ldw8 / w_scale (DECODE pass, M <= 16 only; prefill ignores them,
+ * so the first token's logits equal the bf16 mode's bit for bit). */
+int crab_weight_quant_fp8(crab_ctx* ctx, void* stream, const void* W, int64_t ldw, int N, int K, void* codes, int64_t ld_codes, float* scale);
+
 /* y[M, I] = silu(gu[:, :I]) * gu[:, I:2I]   (modeling_llama.py:269; gate and up packed side by side) */
 int crab_swiglu(crab_ctx* ctx, void* stream, const void* gu, int64_t ldgu, void* y, int64_t ldy, int M, int I);
 
@@ -426,7 +444,11 @@ typedef struct {
     int64_t ldw, ldra, ldb2;
     int32_t N, K, nproj, nl, r, tcols, ucols;
     float scaling;     /* lora_alpha / r */
+    /* optional FP8 form of W ("FP8 decoder weights" above; additions under ABI 13): codes [N, K] (row stride ldw8 bytes) + fp32 [N] row scales.
+     * Honoured by the DECODE pass at M <= 16 only (crab_llama_layer_decode, crab_llama_layers with vt == NULL); NULL: bf16 weights. */
+    const void* W8; int64_t ldw8; const float* w_scale;
 } crab_linear_group;
+int crab_sizeof_linear_group(void);
 
 typedef struct {
     crab_linear_group qkv, o, gu, down;
