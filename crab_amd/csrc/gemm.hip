@@ -191,22 +191,9 @@ __global__ void splitk_epilogue_kernel(const float* __restrict__ part, int S, in
         for (int s = 0; s < S; ++s)
             for (int r = 0; r < w; ++r) v[r] += q[s * MN + r];
     }
-    if (act == ACT_SWIGLU_PAIR) {                         // interleaved (gate, up) columns -> N/2 outputs (N % 4 == 0, no residual)
-        if (bias) { for (int r = 0; r < 4; ++r) v[r] += bf2f(bias[n + r]); }
-        const float o0 = v[0] / (1.0f + __expf(-v[0])) * v[1], o1 = v[2] / (1.0f + __expf(-v[2])) * v[3];
-        const long oc = (long)m * ldc + (n >> 1);
-        if (c_fp32 & CF_C32) { reinterpret_cast<float*>(C)[oc] = o0; reinterpret_cast<float*>(C)[oc + 1] = o1; }
-        else { reinterpret_cast<bf16_t*>(C)[oc] = f2bf(o0); reinterpret_cast<bf16_t*>(C)[oc + 1] = f2bf(o1); }
-        return;
-    }
-    for (int r = 0; r < w; ++r) {
-        float x = v[r];
-        if (bias) x += bf2f(bias[n + r]);
-        x = apply_act(x, act);
-        if (R) x += res_scale * ld_res(R, (long)m * ldr + n + r, c_fp32);
-        if (c_fp32 & CF_C32) reinterpret_cast<float*>(C)[(long)m * ldc + n + r] = x;
-        else reinterpret_cast<bf16_t*>(C)[(long)m * ldc + n + r] = f2bf(x);
-    }
+    // scalar form of gemm_epilogue.h (columns >= N hold 0 and are not stored; the pair: N % 4 == 0, no residual)
+    if (act == ACT_SWIGLU_PAIR) gemm_epilogue_scalar_swiglu(v, m, n, bias, C, ldc, c_fp32);
+    else gemm_epilogue_scalar4(v, m, n, N, bias, act, R, ldr, res_scale, C, ldc, c_fp32);
 }
 
 // SwiGLU-pair fast path of the reduction above (the gate|up projection of the decode step): one thread per 16 interleaved

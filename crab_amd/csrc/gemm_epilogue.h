@@ -1,9 +1,10 @@
-// Shared output stage of the MFMA GEMM kernels (gemm.hip, gemm_glds.hip).
+// Shared output stage of the MFMA GEMM kernels (gemm.hip, gemm_glds.hip) and, in its scalar form (at the end), of the decode GEMMs
+// of skinny.hip and the split-K reduction of gemm.hip.
 //
 // Accumulator layout (operands swapped, see gemm.hip): acc[ni][mi][r] is row m_lane + 16*mi, column n_lane + 16*ni + r,
 // with m_lane = tile row + (lane & 15) and n_lane = tile column + 4 * (lane >> 4).
 //
-// Two forms:
+// Two tile forms:
 //   gemm_epilogue_full    : the wave's whole sub-tile is in range and 8-byte aligned -> no guards, fully unrolled, the
 //                           ACTIVATION IS A TEMPLATE PARAMETER.  With a runtime `act` every one of the TM*TN*4 inlined
 //                           apply_act() switches (erff, two exps) stays in the instruction stream even when act == NONE:
@@ -201,7 +202,7 @@ __device__ __forceinline__ void gemm_epilogue_guarded(const f32x4_t (&acc)[TN][T
     }
 }
 
-// one call site per kernel: picks the unguarded form when this WAVE's sub-tile is interior
+// the one call site of a tile kernel: picks the unguarded form when this WAVE's sub-tile is interior
 template <int TM, int TN>
 __device__ __forceinline__ void gemm_epilogue(const f32x4_t (&acc)[TN][TM], int act, int m_wave, int n_wave, int fr, int fg, int M, int N,
                                               const bf16_t* bias, const bf16_t* R, long ldr, float rs, void* C, long coff, long ldc,
@@ -210,4 +211,36 @@ __device__ __forceinline__ void gemm_epilogue(const f32x4_t (&acc)[TN][TM], int 
                       (!R || ((ldr & 3) == 0));
     if (full) gemm_epilogue_full<TM, TN>(acc, act, m_wave + fr, n_wave + fg * 4, bias, R, ldr, rs, C, coff, ldc, c_fp32);
     else gemm_epilogue_guarded<TM, TN>(acc, act, m_wave + fr, n_wave + fg * 4, M, N, bias, R, ldr, rs, C, coff, ldc, c_fp32);
+}
+
+// ---------------------------------------------------------------------------------------------- scalar form
+// One thread holds the four sums v[0..4) of row m, columns n .. n + 3 (any type indexable by [r]: float[4], f32x4_t): the kernels whose
+// output is a single 16-wide tile per block (skinny.hip) or comes from a workspace (splitk_epilogue_kernel).  Runtime activation, element
+// stores, columns >= N skipped.  The operation order - v + bias, activation, + res_scale * R, one rounding at the store - is the one of
+// the tile forms above.  `flags`: CF_C32 / CF_R32.
+template <typename V4>
+__device__ __forceinline__ void gemm_epilogue_scalar4(const V4& v, int m, int n, int N, const bf16_t* bias, int act, const bf16_t* R, long ldr,
+                                                      float res_scale, void* C, long ldc, int flags) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        if (n + r >= N) break;
+        float x = v[r];
+        if (bias) x += bf2f(bias[n + r]);
+        x = apply_act(x, act);
+        if (R) x += res_scale * ld_res(R, (long)m * ldr + n + r, flags);
+        if (flags & CF_C32) reinterpret_cast<float*>(C)[(long)m * ldc + n + r] = x;
+        else reinterpret_cast<bf16_t*>(C)[(long)m * ldc + n + r] = f2bf(x);
+    }
+}
+
+// ACT_SWIGLU_PAIR: interleaved (gate, up, gate, up) columns -> two outputs at column n / 2 (N % 4 == 0: all four in range; no residual)
+template <typename V4>
+__device__ __forceinline__ void gemm_epilogue_scalar_swiglu(const V4& v, int m, int n, const bf16_t* bias, void* C, long ldc, int flags) {
+    float t[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) t[r] = v[r] + (bias ? bf2f(bias[n + r]) : 0.f);
+    const float o0 = t[0] / (1.0f + __expf(-t[0])) * t[1], o1 = t[2] / (1.0f + __expf(-t[2])) * t[3];
+    const long oc = (long)m * ldc + (n >> 1);
+    if (flags & CF_C32) { reinterpret_cast<float*>(C)[oc] = o0; reinterpret_cast<float*>(C)[oc + 1] = o1; }
+    else { reinterpret_cast<bf16_t*>(C)[oc] = f2bf(o0); reinterpret_cast<bf16_t*>(C)[oc + 1] = f2bf(o1); }
 }

@@ -4,13 +4,16 @@
 // gemm_skinny_dma_kernel (M <= 16, the reference's batch sizes 1 and 8):  C[M,N] = res_scale*R + act(A.B^T + A2.B2^T + bias).
 //   One block per 16 weight rows, 8 waves splitting K; each wave streams its K slice HBM -> LDS by LDS-DMA in whole cache lines
 //   through a private 4-slot ring and reads it back as MFMA fragments (described at the kernel).  5-6.3 TB/s on the wide shapes.
+// gemm_skinny_dma_w8_kernel: the same for the opt-in FP8 (e4m3fn) weights - codes through the ring, converted to bf16 in registers.
+//   The two share, one place per thing: SkRole / sk_role (what a block does, where a lane stages and reads), sk_rope_tail (fused RoPE +
+//   KV append) and sk_store (the output stage).  Each keeps its own ring K loops.
 // gemm_skinny_kernel<MT, NT> (16 < M <= 128 without a split-K workspace; M <= 16 only under tune 1 / 2 / 4 for A/B runs):
 //   One block per 16*NT weight rows (N/16 blocks: 256 for N=4096, i.e. one per CU, 768/1376/2001 for the wider
 //   projections), 8 waves per block splitting K between them.  Each wave streams its K-slice of the 16 weight
 //   rows straight into MFMA A-fragments (global_load_dwordx4, no LDS: every weight byte is used exactly once) and
 //   the matching activation columns into B-fragments (L2-resident, M*K*2 bytes), accumulating 16 x 16*MT fp32.
-//   The 8 partial tiles are reduced through LDS and the epilogue (bias, activation, residual, bf16/fp32 store)
-//   runs once.  No split-K partials ever travel through HBM and the summation order is fixed (deterministic).
+//   The 8 partial tiles are reduced through LDS and the epilogue (the scalar form of gemm_epilogue.h: bias, activation,
+//   residual, bf16/fp32 store) runs once.  No split-K partials ever travel through HBM and the summation order is fixed (deterministic).
 //
 // lora_t_partial_kernel + lora_mix_reduce_kernel: the hyper-LoRA router
 //   T = x.[R;A]^T (N <= 48) is far too skinny for either GEMM grid; it is split over K into `nslices` partial
@@ -20,6 +23,7 @@
 #include "common.h"
 #include "crab_internal.h"
 #include "fp8_common.h"
+#include "gemm_epilogue.h"
 #include <stdlib.h>
 
 namespace {
@@ -138,26 +142,8 @@ __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_kernel(SkinnyP p) {
         f32x4_t v = *reinterpret_cast<const f32x4_t*>(&red[0][t][l][0]);
 #pragma unroll
         for (int w = 1; w < SK_WAVES; ++w) v += *reinterpret_cast<const f32x4_t*>(&red[w][t][l][0]);
-        if (p.act == ACT_SWIGLU_PAIR) {                 // interleaved (gate, up) columns -> two outputs at column n/2
-            float t[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) t[r] = v[r] + (p.bias ? bf2f(p.bias[n + r]) : 0.f);
-            const float o0 = t[0] / (1.0f + __expf(-t[0])) * t[1], o1 = t[2] / (1.0f + __expf(-t[2])) * t[3];
-            const long oc = (long)m * p.ldc + (n >> 1);
-            if (p.c_fp32 & CF_C32) { reinterpret_cast<float*>(p.C)[oc] = o0; reinterpret_cast<float*>(p.C)[oc + 1] = o1; }
-            else { reinterpret_cast<bf16_t*>(p.C)[oc] = f2bf(o0); reinterpret_cast<bf16_t*>(p.C)[oc + 1] = f2bf(o1); }
-            continue;
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            if (n + r >= p.N) break;
-            float x = v[r];
-            if (p.bias) x += bf2f(p.bias[n + r]);
-            x = apply_act(x, p.act);
-            if (p.R) x += p.res_scale * ld_res(p.R, (long)m * p.ldr + n + r, p.c_fp32);
-            if (p.c_fp32 & CF_C32) reinterpret_cast<float*>(p.C)[(long)m * p.ldc + n + r] = x;
-            else reinterpret_cast<bf16_t*>(p.C)[(long)m * p.ldc + n + r] = f2bf(x);
-        }
+        if (p.act == ACT_SWIGLU_PAIR) gemm_epilogue_scalar_swiglu(v, m, n, p.bias, p.C, p.ldc, p.c_fp32);
+        else gemm_epilogue_scalar4(v, m, n, p.N, p.bias, p.act, p.R, p.ldr, p.res_scale, p.C, p.ldc, p.c_fp32);
     }
 }
 
@@ -170,60 +156,145 @@ __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_kernel(SkinnyP p) {
 // 2.3-3.5 TB/s (profiles/README.md).  Here a wave keeps NS x 2 KiB in flight with no register cost, and nothing in the K loop
 // synchronises waves (each wave reads only the ring it fills).  The activation fragments (16 rows x 64 B per k step, L2 / TCP hits)
 // still go straight to registers, issued together with the DMA of their slot so that one counted vmcnt covers both.
+// Block role and staging setup (SkRole) and the fused RoPE + KV-append tail (sk_rope_tail) are shared with the FP8 form below; the
+// plain output stage is the scalar form of gemm_epilogue.h.
 __device__ __attribute__((aligned(16))) uint32_t g_zero_page_sk[64];       // zero-initialised device memory (256 B)
 
 typedef __attribute__((address_space(3))) void* sk_lds_vptr;
 typedef const __attribute__((address_space(1))) void* sk_gbl_vptr;
 
-template <int NT, int NS>
+// What a block of the two LDS-DMA kernels does and where a lane stages / reads its ring slots.  A slot is 16 weight rows x 128 B (64 bf16
+// or 128 FP8 codes per row) in two 1-KiB pieces of 8 rows; a 16-byte chunk holds CH units (8 bf16 elements, or 16 bytes of codes).
+struct SkRole {
+    bool extra;                     // block-uniform: this block owns K range `xe` of the 16 router rows Bx, not rows of B
+    int xe, n0, Nw;                 // first row and row count of the matrix this block streams (Bx: 0, 16)
+    // fused RoPE: block -> (head r_hh, 16-row group r_j); q / k heads take the two 8-row halves of rotation pairs (see SkinnyP)
+    bool rope, r_qk;
+    int r_hh, r_j, r_base, r_half;
+    // staging of piece i: lane l -> row i*8 + (l >> 3) = weight row wrow[i] (clamped: rows >= N are never stored), LDS chunk l & 7
+    // (lane-linear, as LDS-DMA writes), source chunk[i] = (l & 7) ^ ((row >> 1) & 7): the inverse of the swizzle the fragment reads apply
+    long wrow[2];
+    int chunk[2];
+    // fragment offsets inside a slot (units): row fr, source chunk fg (fofs0) / fg + 4 (fofs1) -> LDS chunk ^ ((fr >> 1) & 7)
+    int fofs0, fofs1;
+    // local columns cg*4 .. +3 of the block's tile -> dim inside the head; r_base + dim is the column of the packed projection (= weight row)
+    __device__ __forceinline__ int rope_dim(int cg) const { return r_qk ? (cg >> 1) * r_half + 8 * r_j + (cg & 1) * 4 : 16 * r_j + cg * 4; }
+};
+
+template <int CH>
+__device__ __forceinline__ SkRole sk_role(const SkinnyP& p, int lane) {
+    SkRole k;
+    const int nbN = (p.N + 15) / 16;
+    k.extra = (int)blockIdx.x >= nbN;
+    k.xe = (int)blockIdx.x - nbN;
+    k.Nw = k.extra ? 16 : p.N;
+    k.n0 = k.extra ? 0 : (int)blockIdx.x * 16;
+    k.rope = p.rope_tab != nullptr && !k.extra;
+    const int r_bpd = k.rope ? p.rope_d >> 4 : 1;
+    k.r_hh = (int)blockIdx.x / r_bpd; k.r_j = (int)blockIdx.x % r_bpd;
+    k.r_qk = k.rope && k.r_hh < p.rope_H + p.rope_Hk;
+    k.r_base = k.r_hh * p.rope_d; k.r_half = p.rope_d >> 1;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int row = i * 8 + (lane >> 3);
+        k.chunk[i] = (lane & 7) ^ ((row >> 1) & 7);
+        k.wrow[i] = min(k.n0 + row, k.Nw - 1);
+        if (k.r_qk) k.wrow[i] = k.r_base + (row >> 3) * k.r_half + 8 * k.r_j + (row & 7);
+    }
+    const int fr = lane & 15, fg = lane >> 4;
+    k.fofs0 = fr * 8 * CH + ((fg ^ ((fr >> 1) & 7)) * CH);
+    k.fofs1 = k.fofs0 ^ (4 * CH);
+    return k;
+}
+
+// Fused RoPE + KV append of the packed q|k|v projection (SkinnyP.rope_*): lane l of the reducing wave holds the four reduced sums s[0..4)
+// (before bias) of row l & 15, columns r_base + rope_dim(l >> 4) .. + 3.  The projection value is rounded to bf16 first (what the unfused
+// projection stores: the rotation reads bf16), the rotation partner comes from the lane two column groups away, and rope_lo / rope_hi
+// (common.h) pin the rounding order shared with qkv_rope_split, the prefill tile kernel, the split-K rope reduction and the FP8-KV attention.
+// EVERY lane of the wave must call this - rows >= M included: they take part in the exchange and leave after it.
+template <typename V4>
+__device__ __forceinline__ void sk_rope_tail(const SkinnyP& p, const SkRole& k, int l, const V4& s) {
+    const int m = l & 15, cg = l >> 4;
+    const int d = p.rope_d, pos = p.rope_pos0 + (p.rope_pos_dev ? p.rope_pos_dev[0] : 0);
+    const int dim = k.rope_dim(cg);
+    const int col = k.r_base + dim;
+    float x[4], px[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        x[r] = bf2f(f2bf(s[r] + (p.bias ? bf2f(p.bias[col + r]) : 0.f)));
+        px[r] = __shfl_xor(x[r], 32, 64);                                // the lane two column groups away, same row
+    }
+    if (m >= p.M) return;
+    bf16_t* crow = reinterpret_cast<bf16_t*>(p.C) + (long)m * p.ldc + col;
+    const uint32_t raw0 = pack_bf2(x[0], x[1]), raw1 = pack_bf2(x[2], x[3]);
+    if (!k.r_qk) {                                                   // value head: cache append, the projection row keeps the value
+        const int hk = k.r_hh - p.rope_H - p.rope_Hk;
+        *reinterpret_cast<u32x2*>(crow) = u32x2{raw0, raw1};
+        *reinterpret_cast<u32x2*>(p.rope_vc + (((long)m * p.rope_Hk + hk) * p.rope_Tmax + pos) * d + dim) = u32x2{raw0, raw1};
+        return;
+    }
+    const int idim = 8 * k.r_j + (cg & 1) * 4;                       // index of the rotation pair (first-half dim)
+    const int rp = pos - (p.rope_row_off ? p.rope_row_off[m] : 0);   // rotary position (m < M here); the cache slot stays `pos`
+    const float* cs = p.rope_tab + ((long)rp * k.r_half + idim) * 2;
+    float o[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const float c = cs[2 * r], sn = cs[2 * r + 1];
+        o[r] = cg < 2 ? rope_lo(x[r], px[r], c, sn) : rope_hi(px[r], x[r], c, sn);
+    }
+    const u32x2 ow = {pack_bf2(o[0], o[1]), pack_bf2(o[2], o[3])};
+    if (k.r_hh < p.rope_H) {
+        *reinterpret_cast<u32x2*>(crow) = ow;                        // q rotated in place of the projection row
+    } else {
+        const int hk = k.r_hh - p.rope_H;
+        *reinterpret_cast<u32x2*>(crow) = u32x2{raw0, raw1};         // the row keeps the un-rotated key like the unfused pair
+        *reinterpret_cast<u32x2*>(p.rope_kc + (((long)m * p.rope_Hk + hk) * p.rope_Tmax + pos) * d + dim) = ow;
+    }
+}
+
+// Output stage of one lane of the two LDS-DMA kernels behind the RoPE and router-row cases: v = the four sums of row m, columns n .. n + 3.
+// `part`: fp32 act(sum + bias) + res_scale * R (unrounded) into the slab [M][N] that the row-owning reduction kernels of gemm.hip read
+// (never with the SwiGLU pair epilogue); else the SwiGLU pair; else the plain store.
+template <typename V4>
+__device__ __forceinline__ void sk_store(const SkinnyP& p, float* part, const V4& v, int m, int n) {
+    if (part) gemm_epilogue_scalar4(v, m, n, p.N, p.bias, p.act, p.R, p.ldr, p.res_scale, part, p.N, CF_C32 | (p.c_fp32 & CF_R32));
+    else if (p.act == ACT_SWIGLU_PAIR) gemm_epilogue_scalar_swiglu(v, m, n, p.bias, p.C, p.ldc, p.c_fp32);
+    else gemm_epilogue_scalar4(v, m, n, p.N, p.bias, p.act, p.R, p.ldr, p.res_scale, p.C, p.ldc, p.c_fp32);
+}
+
+// NS = 4 slots of 2 KiB per wave (16 weight rows per block, two blocks resident per CU) is the only instantiation.  Measured alternatives
+// (profiles/README.md): a 6-slot ring changes nothing where a CU holds one block (o, down) and loses where it held two; 32 rows per block
+// (half the activation re-reads) is 10-25 % slower on every shape at M = 1 .. 16.
+template <int NS>
 __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_dma_kernel(SkinnyP p, float* __restrict__ part) {
-    constexpr int SLOT = NT * 16 * 64;                                  // elements: NT x 16 weight rows x 64 k
+    constexpr int SLOT = 16 * 64;                                       // elements: 16 weight rows x 64 k
     __shared__ __attribute__((aligned(16))) bf16_t ring[SK_WAVES][NS][SLOT];
-    __shared__ __attribute__((aligned(16))) float red[SK_WAVES][NT][64][4];
+    __shared__ __attribute__((aligned(16))) float red[SK_WAVES][64][4];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fr = lane & 15, fg = lane >> 4;
-    const int nbN = (p.N + 16 * NT - 1) / (16 * NT);
-    const bool extra = (int)blockIdx.x >= nbN;                          // block-uniform: this block owns a K range of Bx, not rows of B
-    const int xe = (int)blockIdx.x - nbN;                               // which K range
-    const bf16_t* Bw = extra ? p.Bx : p.B;
-    const long ldbw = extra ? p.ldbx : p.ldb;
-    const int Nw = extra ? 16 : p.N;
-    const int n0 = extra ? 0 : (int)blockIdx.x * 16 * NT;
-    // fused RoPE: block -> (head hh, 16-row group j); q / k heads take the two 8-row halves of rotation pairs (see SkinnyP)
-    const bool rope = NT == 1 && p.rope_tab != nullptr && !extra;
-    const int r_bpd = rope ? p.rope_d >> 4 : 1;
-    const int r_hh = (int)blockIdx.x / r_bpd, r_j = (int)blockIdx.x % r_bpd;
-    const bool r_qk = rope && r_hh < p.rope_H + p.rope_Hk;
-    const int r_base = r_hh * p.rope_d, r_half = p.rope_d >> 1;
+    const SkRole k = sk_role<8>(p, lane);                               // units: bf16 elements
+    const bf16_t* Bw = k.extra ? p.Bx : p.B;
+    const long ldbw = k.extra ? p.ldbx : p.ldb;
 
     const int nk1 = (p.K + 63) >> 6;
-    const int nk2 = (p.A2 && !extra) ? (p.K2 + 63) >> 6 : 0;
-    const int kx0 = extra ? (int)((long)nk1 * xe / SKX) : 0;            // first K slot of this block
-    const int ks = extra ? (int)((long)nk1 * (xe + 1) / SKX) - kx0 : nk1 + nk2;
+    const int nk2 = (p.A2 && !k.extra) ? (p.K2 + 63) >> 6 : 0;
+    const int kx0 = k.extra ? (int)((long)nk1 * k.xe / SKX) : 0;        // first K slot of this block
+    const int ks = k.extra ? (int)((long)nk1 * (k.xe + 1) / SKX) - kx0 : nk1 + nk2;
     const int s_begin = kx0 + (int)((long)ks * wave / SK_WAVES), s_end = kx0 + (int)((long)ks * (wave + 1) / SK_WAVES);
     const int nst = s_end - s_begin;
 
-    // staging coordinates of the 2 NT pieces of a slot: lane l -> row i*8 + (l >> 3), LDS chunk l & 7 (lane-linear, as LDS-DMA writes),
-    // source chunk (l & 7) ^ ((row >> 1) & 7): the inverse of the swizzle the fragment reads apply
     const bf16_t* zero = reinterpret_cast<const bf16_t*>(g_zero_page_sk);
-    long off1[2 * NT], off2[2 * NT];
-    int kc[2 * NT];
+    long off1[2], off2[2];
+    int kc[2];
 #pragma unroll
-    for (int i = 0; i < 2 * NT; ++i) {
-        const int row = i * 8 + (lane >> 3);
-        const int c = (lane & 7) ^ ((row >> 1) & 7);
-        long wrow = min(n0 + row, Nw - 1);                              // clamped: rows >= N are never stored
-        if (r_qk) wrow = r_base + (row >> 3) * r_half + 8 * r_j + (row & 7);
-        kc[i] = c * 8;
-        off1[i] = wrow * ldbw + c * 8;
-        off2[i] = wrow * p.ldb2 + c * 8;
+    for (int i = 0; i < 2; ++i) {
+        kc[i] = k.chunk[i] * 8;
+        off1[i] = k.wrow[i] * ldbw + k.chunk[i] * 8;
+        off2[i] = k.wrow[i] * p.ldb2 + k.chunk[i] * 8;
     }
     const long xrow1 = (long)min(fr, p.M - 1) * p.lda, xrow2 = (long)min(fr, p.M - 1) * p.lda2;
     bf16_t* myring = &ring[wave][0][0];
-    // fragment element offsets inside a 16-row tile: row fr, source chunk ks*4 + fg -> LDS chunk (ks*4 + fg) ^ ((fr >> 1) & 7)
-    const int fofs0 = fr * 64 + ((fg ^ ((fr >> 1) & 7)) << 3);
-    const int fofs1 = fofs0 ^ 32;
 
     u32x4 xv[NS][2];
 #define SKD_STAGE(ST_, U_)                                                                                \
@@ -232,7 +303,7 @@ __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_dma_kernel(SkinnyP 
         const bool s2_ = st_ >= nk1;                                                                      \
         const int k0_ = (s2_ ? st_ - nk1 : st_) << 6;                                                     \
         const int Ks_ = s2_ ? p.K2 : p.K;                                                                 \
-        _Pragma("unroll") for (int i = 0; i < 2 * NT; ++i) {                                              \
+        _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                   \
             const bf16_t* src_ = (s2_ ? p.B2 + off2[i] : Bw + off1[i]) + k0_;                             \
             src_ = (k0_ + kc[i] < Ks_) ? src_ : zero;                                                     \
             __builtin_amdgcn_global_load_lds((sk_gbl_vptr)src_, (sk_lds_vptr)(myring + (U_) * SLOT + i * 512), 16, 0, 2);   \
@@ -244,9 +315,7 @@ __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_dma_kernel(SkinnyP 
         }                                                                                                 \
     }
 
-    f32x4_t acc[NT];
-#pragma unroll
-    for (int j = 0; j < NT; ++j) acc[j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int u = 0; u < NS; ++u)
         if (u < nst) SKD_STAGE(s_begin + u, u)
@@ -254,21 +323,15 @@ __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_dma_kernel(SkinnyP 
 #pragma unroll
         for (int u = 0; u < NS; ++u) {
             if (s + u < nst) {
-                // slot s+u has landed once at most the NS-1 younger slots (2 NT + 2 vector-memory instructions each) are outstanding
-                if (s + u + NS - 1 < nst) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 1) * (2 * NT + 2)) : "memory");
+                // slot s+u has landed once at most the NS-1 younger slots (4 vector-memory instructions each) are outstanding
+                if (s + u + NS - 1 < nst) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 1) * 4) : "memory");
                 else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                union { u32x4 r; bf16x8_t f; } w0[NT], w1[NT], x0, x1;
-#pragma unroll
-                for (int j = 0; j < NT; ++j) {
-                    w0[j].r = *reinterpret_cast<const u32x4*>(myring + u * SLOT + j * 1024 + fofs0);
-                    w1[j].r = *reinterpret_cast<const u32x4*>(myring + u * SLOT + j * 1024 + fofs1);
-                }
+                union { u32x4 r; bf16x8_t f; } w0, w1, x0, x1;
+                w0.r = *reinterpret_cast<const u32x4*>(myring + u * SLOT + k.fofs0);
+                w1.r = *reinterpret_cast<const u32x4*>(myring + u * SLOT + k.fofs1);
                 x0.r = xv[u][0]; x1.r = xv[u][1];
-#pragma unroll
-                for (int j = 0; j < NT; ++j) {
-                    acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0[j].f, x0.f, acc[j], 0, 0, 0);
-                    acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1[j].f, x1.f, acc[j], 0, 0, 0);
-                }
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0.f, x0.f, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1.f, x1.f, acc, 0, 0, 0);
                 // the fragments are in registers (the MFMAs consumed them): the ring slot may be refilled
                 asm volatile("" ::: "memory");
                 if (s + u + NS < nst) SKD_STAGE(s_begin + s + u + NS, u)
@@ -276,103 +339,26 @@ __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_dma_kernel(SkinnyP 
         }
     }
 #undef SKD_STAGE
-#pragma unroll
-    for (int j = 0; j < NT; ++j) *reinterpret_cast<f32x4_t*>(&red[wave][j][lane][0]) = acc[j];
+    *reinterpret_cast<f32x4_t*>(&red[wave][lane][0]) = acc;
     __syncthreads();
-    // reduce over waves in fixed order + epilogue: (tile j, lane l): row m = l & 15, cols n0 + 16 j + 4*(l >> 4) + r
-    if (tid < NT * 64) {
-        const int j = tid >> 6, l = tid & 63;
-        const int m = l & 15, n = n0 + j * 16 + (l >> 4) * 4;
-        if (rope) {
-            // every lane of the wave takes part in the partner exchange, rows >= M included
-            f32x4_t v = *reinterpret_cast<const f32x4_t*>(&red[0][0][l][0]);
+    // reduce over waves in fixed order + epilogue: lane l: row m = l & 15, cols n0 + 4*(l >> 4) + r
+    if (tid >= 64) return;
+    const int l = tid;
+    const int m = l & 15, n = k.n0 + (l >> 4) * 4;
+    if (!k.rope && (m >= p.M || n >= k.Nw)) return;                     // RoPE: every lane of the wave takes part in the partner exchange
+    f32x4_t v = *reinterpret_cast<const f32x4_t*>(&red[0][l][0]);
 #pragma unroll
-            for (int w = 1; w < SK_WAVES; ++w) v += *reinterpret_cast<const f32x4_t*>(&red[w][0][l][0]);
-            const int cg = l >> 4;
-            const int d = p.rope_d, pos = p.rope_pos0 + (p.rope_pos_dev ? p.rope_pos_dev[0] : 0);
-            // local columns cg*4 .. +3 of this block's tile -> column of the packed projection
-            const int dim = r_qk ? (cg >> 1) * r_half + 8 * r_j + (cg & 1) * 4 : 16 * r_j + cg * 4;
-            const int col = r_base + dim;
-            float x[4], px[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                x[r] = bf2f(f2bf(v[r] + (p.bias ? bf2f(p.bias[col + r]) : 0.f)));      // what the projection stores: the rotation reads bf16
-                px[r] = __shfl_xor(x[r], 32, 64);                                           // the lane two column groups away, same row
-            }
-            if (m >= p.M) return;
-            bf16_t* crow = reinterpret_cast<bf16_t*>(p.C) + (long)m * p.ldc + col;
-            const uint32_t raw0 = pack_bf2(x[0], x[1]), raw1 = pack_bf2(x[2], x[3]);
-            if (!r_qk) {                                                 // value head: cache append, the projection row keeps the value
-                const int hk = r_hh - p.rope_H - p.rope_Hk;
-                *reinterpret_cast<u32x2*>(crow) = u32x2{raw0, raw1};
-                *reinterpret_cast<u32x2*>(p.rope_vc + (((long)m * p.rope_Hk + hk) * p.rope_Tmax + pos) * d + dim) = u32x2{raw0, raw1};
-                return;
-            }
-            const int idim = 8 * r_j + (cg & 1) * 4;                     // index of the rotation pair (first-half dim)
-            const int rp = pos - (p.rope_row_off ? p.rope_row_off[m] : 0);   // rotary position (m < M here); the cache slot stays `pos`
-            const float* cs = p.rope_tab + ((long)rp * r_half + idim) * 2;
-            float o[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float c = cs[2 * r], sn = cs[2 * r + 1];
-                o[r] = cg < 2 ? rope_lo(x[r], px[r], c, sn) : rope_hi(px[r], x[r], c, sn);
-            }
-            const u32x2 ow = {pack_bf2(o[0], o[1]), pack_bf2(o[2], o[3])};
-            if (r_hh < p.rope_H) {
-                *reinterpret_cast<u32x2*>(crow) = ow;                    // q rotated in place of the projection row
-            } else {
-                const int hk = r_hh - p.rope_H;
-                *reinterpret_cast<u32x2*>(crow) = u32x2{raw0, raw1};     // the row keeps the un-rotated key like the unfused pair
-                *reinterpret_cast<u32x2*>(p.rope_kc + (((long)m * p.rope_Hk + hk) * p.rope_Tmax + pos) * d + dim) = ow;
-            }
-            return;
-        }
-        if (m >= p.M || n >= Nw) return;
-        f32x4_t v = *reinterpret_cast<const f32x4_t*>(&red[0][j][l][0]);
-#pragma unroll
-        for (int w = 1; w < SK_WAVES; ++w) v += *reinterpret_cast<const f32x4_t*>(&red[w][j][l][0]);
-        if (extra) {                                    // partial router product x . [R;A]^T over this block's K range, fp32 [SKX][16][16]
-            *reinterpret_cast<f32x4_t*>(p.Tx + ((long)xe * 16 + m) * 16 + n) = v;
-            return;
-        }
-        if (part) {                                     // fp32 act(sum + bias) + res_scale * R (unrounded) for the row-owning reduction
-            float* o = part + (long)m * p.N + n;        // kernel of gemm.hip, slab layout [M][N]; never with the SwiGLU pair epilogue
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (n + r >= p.N) break;
-                float x = v[r];
-                if (p.bias) x += bf2f(p.bias[n + r]);
-                x = apply_act(x, p.act);
-                if (p.R) x += p.res_scale * ld_res(p.R, (long)m * p.ldr + n + r, p.c_fp32);
-                o[r] = x;
-            }
-            return;
-        }
-        if (p.act == ACT_SWIGLU_PAIR) {                 // interleaved (gate, up) columns -> two outputs at column n/2
-            float t[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) t[r] = v[r] + (p.bias ? bf2f(p.bias[n + r]) : 0.f);
-            const float o0 = t[0] / (1.0f + __expf(-t[0])) * t[1], o1 = t[2] / (1.0f + __expf(-t[2])) * t[3];
-            const long oc = (long)m * p.ldc + (n >> 1);
-            if (p.c_fp32 & CF_C32) { reinterpret_cast<float*>(p.C)[oc] = o0; reinterpret_cast<float*>(p.C)[oc + 1] = o1; }
-            else { reinterpret_cast<bf16_t*>(p.C)[oc] = f2bf(o0); reinterpret_cast<bf16_t*>(p.C)[oc + 1] = f2bf(o1); }
-            return;
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            if (n + r >= p.N) break;
-            float x = v[r];
-            if (p.bias) x += bf2f(p.bias[n + r]);
-            x = apply_act(x, p.act);
-            if (p.R) x += p.res_scale * ld_res(p.R, (long)m * p.ldr + n + r, p.c_fp32);
-            if (p.c_fp32 & CF_C32) reinterpret_cast<float*>(p.C)[(long)m * p.ldc + n + r] = x;
-            else reinterpret_cast<bf16_t*>(p.C)[(long)m * p.ldc + n + r] = f2bf(x);
-        }
+    for (int w = 1; w < SK_WAVES; ++w) v += *reinterpret_cast<const f32x4_t*>(&red[w][l][0]);
+    if (k.rope) { sk_rope_tail(p, k, l, v); return; }
+    if (k.extra) {                                      // partial router product x . [R;A]^T over this block's K range, fp32 [SKX][16][16]
+        *reinterpret_cast<f32x4_t*>(p.Tx + ((long)k.xe * 16 + m) * 16 + n) = v;
+        return;
     }
+    sk_store(p, part, v, m, n);
 }
 
 // ---------------------------------------------------------------------------------------------- M <= 16: FP8 weights through LDS
-// gemm_skinny_dma_w8_kernel: gemm_skinny_dma_kernel<1, 4> for weights stored as e4m3fn codes + one fp32 scale per weight row (w8.hip; W8A16:
+// gemm_skinny_dma_w8_kernel: gemm_skinny_dma_kernel<4> for weights stored as e4m3fn codes + one fp32 scale per weight row (w8.hip; W8A16:
 // the activations stay bf16).  Same grid (one block per 16 weight rows + the SKX ride-along blocks), same 8 waves splitting K, same
 // wave-private ring of NS 2-KiB slots filled by LDS-DMA in 1-KiB pieces of 8 rows x 128 B - whole cache lines of a row - and read back with
 // the same XOR swizzle.  A slot of codes therefore spans 128 k (a bf16 slot: 64), its fragment reads return 16 codes per lane which are
@@ -384,7 +370,7 @@ __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_dma_kernel(SkinnyP 
 // rows, bf16, unscaled) run whole bf16 slots, in a ring loop of their own behind the loop over the codes.  K tail: 16-byte pieces past K come from the zero
 // page; K % 16 == 8 leaves 8 foreign bytes in the last piece of a row (ld_codes % 16 == 0 keeps them inside the row), masked after the read.
 // The per-wave partial tiles are reduced through the ring's own storage (every wave has consumed its slots): 64 KiB of LDS per block.
-// Every epilogue is the bf16 kernel's, with the row scale applied to the reduced main sum.
+// Epilogues: the shared ones (sk_rope_tail, sk_store), with the row scale applied to the reduced main sum.
 template <int NS>
 __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_dma_w8_kernel(SkinnyP p, float* __restrict__ part) {
     constexpr int SLOTB = 16 * 128;                                     // bytes: 16 weight rows x 128 B
@@ -393,46 +379,31 @@ __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_dma_w8_kernel(Skinn
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fr = lane & 15, fg = lane >> 4;
-    const int nbN = (p.N + 15) / 16;
-    const bool extra = (int)blockIdx.x >= nbN;                          // block-uniform: this block owns a K range of Bx (bf16), not rows of B
-    const int xe = (int)blockIdx.x - nbN;
-    const int Nw = extra ? 16 : p.N;
-    const int n0 = extra ? 0 : (int)blockIdx.x * 16;
-    const bool rope = p.rope_tab != nullptr && !extra;
-    const int r_bpd = rope ? p.rope_d >> 4 : 1;
-    const int r_hh = (int)blockIdx.x / r_bpd, r_j = (int)blockIdx.x % r_bpd;
-    const bool r_qk = rope && r_hh < p.rope_H + p.rope_Hk;
-    const int r_base = r_hh * p.rope_d, r_half = p.rope_d >> 1;
+    const SkRole k = sk_role<16>(p, lane);                              // units: bytes
 
     // slots of this block: extra - the 64-wide bf16 slots [kx0, kx0 + ks) of Bx (the K ranges of the bf16 kernel: the consumer adds the SKX
     // partials in order); else nk8 128-wide slots of codes, then nk2 64-wide bf16 slots of B2
     const int nk64 = (p.K + 63) >> 6;
-    const int nk8 = extra ? 0 : (p.K + 127) >> 7;
-    const int nk2 = (p.A2 && !extra) ? (p.K2 + 63) >> 6 : 0;
-    const int kx0 = extra ? (int)((long)nk64 * xe / SKX) : 0;
-    const int ks = extra ? (int)((long)nk64 * (xe + 1) / SKX) - kx0 : nk8 + nk2;
+    const int nk8 = k.extra ? 0 : (p.K + 127) >> 7;
+    const int nk2 = (p.A2 && !k.extra) ? (p.K2 + 63) >> 6 : 0;
+    const int kx0 = k.extra ? (int)((long)nk64 * k.xe / SKX) : 0;
+    const int ks = k.extra ? (int)((long)nk64 * (k.xe + 1) / SKX) - kx0 : nk8 + nk2;
     const int s_begin = kx0 + (int)((long)ks * wave / SK_WAVES), s_end = kx0 + (int)((long)ks * (wave + 1) / SK_WAVES);
     const int nst = s_end - s_begin;
 
-    // staging coordinates of the 2 pieces of a slot (bytes): lane l -> row i*8 + (l >> 3), LDS chunk l & 7, source chunk (l & 7) ^ ((row >> 1) & 7)
     const uint8_t* zero = reinterpret_cast<const uint8_t*>(g_zero_page_sk);
     long off8[2], offb[2], off2[2];
     int kc[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-        const int row = i * 8 + (lane >> 3);
-        const int c = (lane & 7) ^ ((row >> 1) & 7);
-        long wrow = min(n0 + row, Nw - 1);                              // clamped: rows >= N are never stored
-        if (r_qk) wrow = r_base + (row >> 3) * r_half + 8 * r_j + (row & 7);
-        kc[i] = c;
-        off8[i] = wrow * p.ldb8 + c * 16;                               // codes: 16 k per chunk
-        offb[i] = (long)(extra ? row : 0) * p.ldbx + c * 8;             // Bx rows (bf16 elements): 8 k per chunk
-        off2[i] = wrow * p.ldb2 + c * 8;
+        kc[i] = k.chunk[i];
+        off8[i] = k.wrow[i] * p.ldb8 + k.chunk[i] * 16;                 // codes: 16 k per chunk
+        offb[i] = (long)(k.extra ? i * 8 + (lane >> 3) : 0) * p.ldbx + k.chunk[i] * 8;  // Bx rows (bf16 elements): 8 k per chunk
+        off2[i] = k.wrow[i] * p.ldb2 + k.chunk[i] * 8;
     }
     const long xrow1 = (long)min(fr, p.M - 1) * p.lda, xrow2 = (long)min(fr, p.M - 1) * p.lda2;
     uint8_t* myring = &ring[wave][0][0];
-    const int fofs0 = fr * 128 + ((fg ^ ((fr >> 1) & 7)) << 4);         // bytes: row fr, source chunk fg -> LDS chunk fg ^ ((fr >> 1) & 7)
-    const int fofs1 = fofs0 ^ 64;                                       // source chunk fg + 4
+    const int fofs0 = k.fofs0, fofs1 = k.fofs1;
     // A wave's slots [s_begin, s_end) are first its slots of codes, then its bf16 slots: two ring loops, each with ONE kind of slot - a
     // fixed number of vector-memory instructions per slot, so a counted vmcnt says when a slot has landed - and no branch on the kind
     // inside either (a join inside the loop makes the compiler's wait-count pass drain the ring).  Only the wave that owns the K-extension
@@ -492,7 +463,7 @@ __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_dma_w8_kernel(Skinn
     }
     if (nb > 0) {                                                       // wave-uniform
         // the bf16 slots, exactly as gemm_skinny_dma_kernel runs them: 64 k per slot, 2 DMA pieces + 2 activation fragments
-        const bool s2 = !extra;
+        const bool s2 = !k.extra;
         const int Ks = s2 ? p.K2 : p.K;
         const bf16_t* zb = reinterpret_cast<const bf16_t*>(zero);
         const bf16_t* wb0 = s2 ? p.B2 + off2[0] : p.Bx + offb[0];
@@ -541,7 +512,7 @@ __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_dma_w8_kernel(Skinn
     __syncthreads();
     if (tid >= 64) return;
     const int l = tid;
-    const int m = l & 15, n = n0 + (l >> 4) * 4;
+    const int m = l & 15, n = k.n0 + (l >> 4) * 4;
     f32x4_t v8 = *reinterpret_cast<const f32x4_t*>(reinterpret_cast<const float*>(&ring[0][0][0]) + l * 4);
     f32x4_t vb = *reinterpret_cast<const f32x4_t*>(reinterpret_cast<const float*>(&ring[0][0][0]) + 256 + l * 4);
 #pragma unroll
@@ -549,89 +520,23 @@ __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_dma_w8_kernel(Skinn
         v8 += *reinterpret_cast<const f32x4_t*>(reinterpret_cast<const float*>(&ring[w][0][0]) + l * 4);
         vb += *reinterpret_cast<const f32x4_t*>(reinterpret_cast<const float*>(&ring[w][0][0]) + 256 + l * 4);
     }
-    if (rope) {
-        // every lane of the wave takes part in the partner exchange, rows >= M included
-        const int cg = l >> 4;
-        const int d = p.rope_d, pos = p.rope_pos0 + (p.rope_pos_dev ? p.rope_pos_dev[0] : 0);
-        // local columns cg*4 .. +3 of this block's tile -> column of the packed projection = the weight row they came from (its scale)
-        const int dim = r_qk ? (cg >> 1) * r_half + 8 * r_j + (cg & 1) * 4 : 16 * r_j + cg * 4;
-        const int col = r_base + dim;
-        float x[4], px[4];
+    if (k.rope) {
+        const int col = k.r_base + k.rope_dim(l >> 4);              // the weight row the lane's columns came from (its scale)
+        float t[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float t = __fmaf_rn(p.bscale[col + r], v8[r], vb[r]);
-            x[r] = bf2f(f2bf(t + (p.bias ? bf2f(p.bias[col + r]) : 0.f)));          // what the projection stores: the rotation reads bf16
-            px[r] = __shfl_xor(x[r], 32, 64);                                       // the lane two column groups away, same row
-        }
-        if (m >= p.M) return;
-        bf16_t* crow = reinterpret_cast<bf16_t*>(p.C) + (long)m * p.ldc + col;
-        const uint32_t raw0 = pack_bf2(x[0], x[1]), raw1 = pack_bf2(x[2], x[3]);
-        if (!r_qk) {                                                 // value head: cache append, the projection row keeps the value
-            const int hk = r_hh - p.rope_H - p.rope_Hk;
-            *reinterpret_cast<u32x2*>(crow) = u32x2{raw0, raw1};
-            *reinterpret_cast<u32x2*>(p.rope_vc + (((long)m * p.rope_Hk + hk) * p.rope_Tmax + pos) * d + dim) = u32x2{raw0, raw1};
-            return;
-        }
-        const int idim = 8 * r_j + (cg & 1) * 4;                     // index of the rotation pair (first-half dim)
-        const int rp = pos - (p.rope_row_off ? p.rope_row_off[m] : 0);   // rotary position (m < M here); the cache slot stays `pos`
-        const float* cs = p.rope_tab + ((long)rp * r_half + idim) * 2;
-        float o[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float c = cs[2 * r], sn = cs[2 * r + 1];
-            o[r] = cg < 2 ? rope_lo(x[r], px[r], c, sn) : rope_hi(px[r], x[r], c, sn);
-        }
-        const u32x2 ow = {pack_bf2(o[0], o[1]), pack_bf2(o[2], o[3])};
-        if (r_hh < p.rope_H) {
-            *reinterpret_cast<u32x2*>(crow) = ow;                    // q rotated in place of the projection row
-        } else {
-            const int hk = r_hh - p.rope_H;
-            *reinterpret_cast<u32x2*>(crow) = u32x2{raw0, raw1};     // the row keeps the un-rotated key like the unfused pair
-            *reinterpret_cast<u32x2*>(p.rope_kc + (((long)m * p.rope_Hk + hk) * p.rope_Tmax + pos) * d + dim) = ow;
-        }
+        for (int r = 0; r < 4; ++r) t[r] = __fmaf_rn(p.bscale[col + r], v8[r], vb[r]);
+        sk_rope_tail(p, k, l, t);
         return;
     }
-    if (m >= p.M || n >= Nw) return;
-    if (extra) {                                        // partial router product x . [R;A]^T over this block's K range, fp32 [SKX][16][16]
-        *reinterpret_cast<f32x4_t*>(p.Tx + ((long)xe * 16 + m) * 16 + n) = vb;
+    if (m >= p.M || n >= k.Nw) return;
+    if (k.extra) {                                      // partial router product x . [R;A]^T over this block's K range, fp32 [SKX][16][16]
+        *reinterpret_cast<f32x4_t*>(p.Tx + ((long)k.xe * 16 + m) * 16 + n) = vb;
         return;
     }
     float v[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) v[r] = n + r < p.N ? __fmaf_rn(p.bscale[n + r], v8[r], vb[r]) : 0.f;
-    if (part) {                                         // fp32 act(sum + bias) + res_scale * R (unrounded) for the row-owning reduction
-        float* o = part + (long)m * p.N + n;            // kernel of gemm.hip, slab layout [M][N]; never with the SwiGLU pair epilogue
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            if (n + r >= p.N) break;
-            float x = v[r];
-            if (p.bias) x += bf2f(p.bias[n + r]);
-            x = apply_act(x, p.act);
-            if (p.R) x += p.res_scale * ld_res(p.R, (long)m * p.ldr + n + r, p.c_fp32);
-            o[r] = x;
-        }
-        return;
-    }
-    if (p.act == ACT_SWIGLU_PAIR) {                     // interleaved (gate, up) columns -> two outputs at column n/2
-        float t[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) t[r] = v[r] + (p.bias ? bf2f(p.bias[n + r]) : 0.f);
-        const float o0 = t[0] / (1.0f + __expf(-t[0])) * t[1], o1 = t[2] / (1.0f + __expf(-t[2])) * t[3];
-        const long oc = (long)m * p.ldc + (n >> 1);
-        if (p.c_fp32 & CF_C32) { reinterpret_cast<float*>(p.C)[oc] = o0; reinterpret_cast<float*>(p.C)[oc + 1] = o1; }
-        else { reinterpret_cast<bf16_t*>(p.C)[oc] = f2bf(o0); reinterpret_cast<bf16_t*>(p.C)[oc + 1] = f2bf(o1); }
-        return;
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        if (n + r >= p.N) break;
-        float x = v[r];
-        if (p.bias) x += bf2f(p.bias[n + r]);
-        x = apply_act(x, p.act);
-        if (p.R) x += p.res_scale * ld_res(p.R, (long)m * p.ldr + n + r, p.c_fp32);
-        if (p.c_fp32 & CF_C32) reinterpret_cast<float*>(p.C)[(long)m * p.ldc + n + r] = x;
-        else reinterpret_cast<bf16_t*>(p.C)[(long)m * p.ldc + n + r] = f2bf(x);
-    }
+    sk_store(p, part, v, m, n);
 }
 
 // ---------------------------------------------------------------------------------------------- hyper-LoRA router
@@ -973,9 +878,6 @@ int crab_gemm_skinny_launch(crab_ctx* ctx, hipStream_t s, const crab_gemm_desc* 
     // M <= 16: the LDS-DMA ring kernel (tune 1 / 2 / 4 keep the register-direct kernel for A/B runs); d->tune == 9: the same with
     // raw fp32 sums to the workspace (used by crab_gemm_bf16 for its fused reduction epilogues)
     if (d->M <= 16 && (d->tune == 0 || d->tune == 9) && (d->ldb & 7) == 0 && (!d->A2 || (d->ldb2 & 7) == 0)) {
-        // <NT = 1, NS = 4>: 16 weight rows per block, 4 slots of 2 KiB per wave, two blocks resident per CU.  Measured alternatives
-        // (profiles/README.md): a 6-slot ring changes nothing where a CU holds one block (o, down) and loses where it held two;
-        // 32 rows per block (half the activation re-reads) is 10-25 % slower on every shape at M = 1 .. 16.
         float* part = d->tune == 9 ? (float*)d->workspace : nullptr;
         int extra_blocks = 0;
         if (d->tune == 9 && d->lora_RA) {               // the projection's own router rows ride on this launch (rowfin.hip applies them)
@@ -987,7 +889,7 @@ int crab_gemm_skinny_launch(crab_ctx* ctx, hipStream_t s, const crab_gemm_desc* 
             hipLaunchKernelGGL((gemm_skinny_dma_w8_kernel<4>), dim3((d->N + 15) / 16 + extra_blocks), dim3(SK_WAVES * 64), 0, s, p, part);
             return crab_check_launch(ctx, "gemm_skinny_dma_w8_kernel");
         }
-        hipLaunchKernelGGL((gemm_skinny_dma_kernel<1, 4>), dim3((d->N + 15) / 16 + extra_blocks), dim3(SK_WAVES * 64), 0, s, p, part);
+        hipLaunchKernelGGL((gemm_skinny_dma_kernel<4>), dim3((d->N + 15) / 16 + extra_blocks), dim3(SK_WAVES * 64), 0, s, p, part);
         return crab_check_launch(ctx, "gemm_skinny_dma_kernel");
     }
     if (d->B8) return crab_fail(ctx, CRAB_E_UNSUPPORTED, "gemm: FP8 weights (B8) need the M <= 16 LDS-DMA kernel (tune 0 / 9, ldb and ldb2 multiples of 8)");

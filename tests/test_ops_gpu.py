@@ -535,6 +535,44 @@ def test_gemm_small_batch_lds_dma_kernel(M, N, K, K2):
     assert torch.equal(ops.gemm(x, w, bias=b, residual=r, x2=x2, w2=w2, out_fp32=True), y), "non-deterministic"
 
 
+_SCALAR_STAGE = {}
+
+
+def _scalar_stage_problem(M, K):
+    """N = 100, a K-extension of 32, a bias and a residual; the float64 results of the gelu (with residual) and SwiGLU-pair (without) forms.
+    Built once per (M, K) and shared by the cases below, which only read it."""
+    if (M, K) not in _SCALAR_STAGE:
+        N, K2 = 100, 32
+        x, w, b, r = _rand(M, K, seed=41), _rand(N, K, seed=42, scale=K ** -0.5), _rand(N, seed=43), _rand(M, N, seed=44)
+        x2, w2 = _rand(M, K2, seed=45), _rand(N, K2, seed=46, scale=0.1)
+        z = x.double() @ w.double().t() + x2.double() @ w2.double().t() + b.double()
+        ref = {"gelu": F.gelu(z) + r.double(), "swiglu_pair": F.silu(z[:, 0::2]) * z[:, 1::2]}
+        _SCALAR_STAGE[(M, K)] = ({k: v.cuda() for k, v in dict(x=x, w=w, bias=b, x2=x2, w2=w2).items()}, r.cuda(), ref)
+    return _SCALAR_STAGE[(M, K)]
+
+
+@pytest.mark.parametrize("act", ["gelu", "swiglu_pair"])
+@pytest.mark.parametrize("M,tune,K,kernel", [(5, 0, 72, "gemm_skinny_dma_kernel"), (5, 1, 72, "gemm_skinny_kernel"), (40, 0, 72, "gemm_skinny_kernel"),
+                                             (64, 104, 72, "gemm_bt_kernel(split-K)"), (64, 104, 1032, "splitk_epilogue_kernel")])
+def test_gemm_scalar_output_stage_call_sites(M, tune, K, kernel, act):
+    """One problem (N = 100: a ragged last 16-column tile; K = 72: K % 16 == 8; K-extension, bias, residual) through the call sites of the
+    scalar output stage of gemm_epilogue.h: the LDS-DMA kernel (M = 5), the register-direct kernel at one and at four row tiles (M = 5 under
+    tune 1, M = 40) and the split-K reduction (M = 64 under tune 104).  At K = 72 the problem has three K tiles and the library takes no
+    split, so that case ends in the tile kernel's own epilogue; K = 1032 (still K % 16 == 8) is the same problem with enough tiles for the
+    four slices and is the case that runs splitk_epilogue_kernel.  fp32 output against float64 to TOL_F32, and the bf16 output must be the
+    rounded fp32 output exactly (one rounding, at the store)."""
+    from crab_amd import ops
+    dv, r, ref = _scalar_stage_problem(M, K)
+    kw = dict(dv, act=act, tune=tune, **({} if act == "swiglu_pair" else {"residual": r}))
+    x, w = kw.pop("x"), kw.pop("w")
+    with ops.launch_trace(0) as tr:
+        y32 = ops.gemm(x, w, out_fp32=True, **kw)
+    assert tr.launched(kernel) == 1, tr.counts
+    _cmp(y32, ref[act], TOL_F32, f"scalar stage {kernel} M={M} K={K} {act}")
+    yb = ops.gemm(x, w, **kw)
+    assert yb.dtype == BF and torch.equal(yb, y32.to(BF)), "bf16 output is not the rounded fp32 output"
+
+
 @pytest.mark.parametrize("M,tune", [(17, 0), (64, 0), (64, 104), (64, 208), (128, 0), (100, 103), (33, 102), (256, 403), (200, 407), (256, 0)])
 def test_gemm_splitk_decode_regime(M, tune):
     """16 < M <= 256 with the caller workspace: split-K tiled kernels (tune 4xx: 256x256 ring kernel with K slices, ragged N / K
