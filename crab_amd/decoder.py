@@ -13,6 +13,7 @@ token position, step index and finished flags live in device memory, so there is
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from dataclasses import dataclass
 from typing import List, Optional
@@ -34,6 +35,7 @@ RAGGED_PAD_MAX = 0.06     # a coalesced wave whose batches differ in length is p
 WEIGHT_DTYPES = ("bf16", "fp8_e4m3")       # GenerationEngine(weight_dtype=...): bf16 decoder weights | opt-in FP8 (e4m3fn codes + fp32 row scales) for decode steps of <= 16 rows
 W8_MAX_ROWS = 16                            # rows up to which a decode step streams the FP8 weights (the regime of gemm_skinny_dma_w8_kernel, csrc/skinny.hip)
 KV_CACHE_DTYPES = ("bf16", "fp8_e4m3")     # GenerationEngine(kv_cache_dtype=...): the default bf16 cache | the opt-in FP8 (OCP e4m3fn) cache with fp32 row scales
+EOS_CHECK_EVERY = 16      # decode steps between two host reads of the `finished` flags: the only synchronisation inside the step loop (_run_steps)
 NATIVE_LAYERS = True      # False: issue every launch of a layer from Python (A/B runs and the sequencer-equivalence tests)
 
 
@@ -154,6 +156,45 @@ class _Workspace:
         self.attn_ws = ops.attn_decode_rope_workspace(M, H, d, device) if M * H < ops.ATTN_SPLIT_BELOW and d in (64, 128) else None
 
 
+@contextlib.contextmanager
+def _ws_slot(slot: int):
+    """ops.WS_SLOT = slot for the launches issued (or captured) inside; the previous value is back on any exit."""
+    saved, ops.WS_SLOT = ops.WS_SLOT, slot
+    try:
+        yield
+    finally:
+        ops.WS_SLOT = saved
+
+
+def _trim_at_eos(out_ids: torch.Tensor, n_done: int, eos: int) -> torch.Tensor:
+    """The first n_done columns of out_ids [B, n], cut after the first column at which EVERY row has emitted `eos` (HF stops a call as soon as
+    all of its rows have finished; the columns behind it were produced between two checks).  eos < 0: no stop id.  A view: callers clone."""
+    out = out_ids[:, :n_done]
+    if eos >= 0:
+        idx = torch.nonzero(((out == eos).int().cumsum(1) > 0).all(0))
+        if idx.numel():
+            out = out[:, : int(idx[0].item()) + 1]
+    return out
+
+
+def _pack_waves(Bs: List[int], cap: int) -> List[List[int]]:
+    """generate_many(coalesce=True): the batches (Bs[g] rows each), in order, as waves of at most `cap` rows and about equal size - 60 batches
+    of 8 at cap 448 run as 240 + 240, not 448 + 32.  A batch larger than the cap is a wave of its own.  Returns the batch indices per wave."""
+    total = sum(Bs)
+    n_waves = max(1, -(-total // cap))
+    target = -(-total // n_waves)
+    waves, cur, rows = [], [], 0
+    for g, b in enumerate(Bs):
+        if cur and rows + b > min(cap, max(target, b)):
+            waves.append(cur)
+            cur, rows = [], 0
+        cur.append(g)
+        rows += b
+    if cur:
+        waves.append(cur)
+    return waves
+
+
 class GenerationEngine:
     """Prefill + greedy decode over a DecoderModel + lm_head.  Owns KV caches / workspaces (torch allocator)."""
 
@@ -170,7 +211,6 @@ class GenerationEngine:
         self._stage = None             # fp8 mode: the bf16 staging pair a prefill chunk runs into (flat, grow-only)
         self.kv_cache_dtype = kv_cache_dtype
         self.weight_dtype = weight_dtype
-        self._w_depth = 0
         self._w_used = None            # weight dtype the decode states of the call in progress were built for (last_plan["weight_dtype_used"])
         self.cfg = model.config
         self._rope = None
@@ -234,25 +274,24 @@ class GenerationEngine:
         finally:
             self._kv_mode = saved
 
-    def _with_modes(self, kv_cache_dtype, weight_dtype, fn, *a, **k):
-        """_with_kv_mode for both per-call modes; both values are checked before either is set, so a refused call changes nothing.  The outermost
-        call also stamps last_plan with the weight dtype its decode states ran with ("bf16" when a decode batch exceeded 16 rows)."""
+    def _call(self, kv_cache_dtype, weight_dtype, fn, *a, **k):
+        """The one entry of generate() / generate_many(): fn under both per-call modes (both values are checked before either is set, so a
+        refused call changes nothing) and under the one retry (_retry_after_eviction), then last_plan is stamped with the weight dtype the
+        call's decode states ran with ("bf16" when a decode batch exceeded 16 rows).  Nothing inside the engine comes back here - a single
+        batch of generate_many, a lone coalesced wave and the groups of a split batch call _generate - so there is one verdict and one retry
+        per call by construction."""
         if kv_cache_dtype is not None:
             self.check_kv_cache_dtype(kv_cache_dtype)
         saved = self._w_mode
         if weight_dtype is not None:
             self._w_mode = self.check_weight_dtype(weight_dtype)
-        outer = self._w_depth == 0                  # generate_many / a split generate() call generate() themselves: one verdict for the whole call
-        if outer:
-            self._w_used = None
-        self._w_depth += 1
+        self._w_used = None
         try:
-            res = self._with_kv_mode(kv_cache_dtype, fn, *a, **k)
-            if outer and isinstance(self.last_plan, dict):
+            res = self._with_kv_mode(kv_cache_dtype, self._retry_after_eviction, fn, *a, **k)
+            if isinstance(self.last_plan, dict):
                 self.last_plan["weight_dtype_used"] = self._w_used or "bf16"
             return res
         finally:
-            self._w_depth -= 1
             self._w_mode = saved
 
     def _staging(self, n: int, S: int):
@@ -1013,10 +1052,14 @@ class GenerationEngine:
         for n in chunks:
             self._prefill_chunk(st, embeds[b0:b0 + n], b0)
             b0 += n
+        return self._first_token(st, sink)
+
+    def _first_token(self, st: "_DecodeState", sink=None) -> "_DecodeState":
+        """The tail of every start: the prefill's logits / hidden rows to the sink, then the first token selected from them."""
         if sink is not None:
             sink(st)
         self._select(st)
-        ops.advance(st.pos_dev, st.step_dev)           # pos: S-1 -> S (position of the token just selected), step: 0 -> 1
+        ops.advance(st.pos_dev, st.step_dev)           # pos: S-1 -> S (the slot of the token just selected; Smax-1 -> Smax in a ragged state), step: 0 -> 1
         return st
 
     def _prefill_groups(self, st, embeds_list, Bs, Ss, Smax):
@@ -1086,11 +1129,7 @@ class GenerationEngine:
         else:
             self.last_ragged_prefill = "per_group"
             self._prefill_groups(st, embeds_list, Bs, Ss, Smax)
-        if sink is not None:
-            sink(st)
-        self._select(st)
-        ops.advance(st.pos_dev, st.step_dev)           # slot: Smax-1 -> Smax, step: 0 -> 1
-        return st
+        return self._first_token(st, sink)
 
     def _retry_after_eviction(self, fn, *a, **k):
         """memory_budget() counts the KV caches of stale slots (left by an earlier generate_many / decode_streams > 1) as reclaimable, but
@@ -1115,8 +1154,57 @@ class GenerationEngine:
                  return_step_logits: bool = False, return_hidden: bool = False, decode_streams: int = 1,
                  return_first_logits: bool = False, sampling=None, kv_cache_dtype: Optional[str] = None, weight_dtype: Optional[str] = None):
         """kv_cache_dtype / weight_dtype: "bf16" / "fp8_e4m3" for this call (None: the engine's); see _generate for the rest."""
-        return self._with_modes(kv_cache_dtype, weight_dtype, self._retry_after_eviction, self._generate, embeds, max_new_tokens, eos_token_id, pad_token_id,
-                                  min_new_tokens, prefill_chunk, use_graph, return_step_logits, return_hidden, decode_streams, return_first_logits, sampling)
+        return self._call(kv_cache_dtype, weight_dtype, self._generate, embeds, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens,
+                          prefill_chunk, use_graph, return_step_logits, return_hidden, decode_streams, return_first_logits, sampling)
+
+    def _run_steps(self, sts: List["_DecodeState"], max_new_tokens: int, graphed: bool, side_streams: bool, retire: bool, on_step=None,
+                   sampled_step=None):
+        """The decode steps 1 .. max_new_tokens - 1 of started states (step 0, the first token, is _start's): THE step loop of the engine.
+        graphed: every state's step is captured under its own scratch slot (or its graph reused, _capture) and replayed; else the step runs
+        eagerly.  side_streams: every state steps on a HIP stream of its own, forked from the current stream before the first step and joined
+        to it after the last; else all steps go to the current stream.  The loop holds no host synchronisation but the EOS check: every
+        EOS_CHECK_EVERY steps the `finished` flags are read, and
+          retire = True:  a state whose rows have all finished stops stepping (generate_many: HF stops that call);
+          retire = False: every state keeps stepping until ALL of them have finished (generate(decode_streams > 1): the groups are one call,
+                          their buffers are joined column by column).
+        on_step(sts[0]) runs after every step.  sampled_step(step, sts[0]) is asked before every graphed step of the FIRST state and returns
+        True when it has run that step itself (bench.py's roofline sampling); the state is device-resident, so replays continue after it."""
+        main = torch.cuda.current_stream()
+        graphs, streams = [], []
+        for st in sts:
+            with _ws_slot(st.slot):
+                graphs.append(self._capture(st) if graphed else None)
+            streams.append(torch.cuda.Stream() if side_streams else main)
+        if side_streams:
+            for sg in streams:
+                sg.wait_stream(main)
+        eos_on = sts[0].eos >= 0
+        live = list(range(len(sts)))
+        for step in range(1, max_new_tokens):
+            for g in live:
+                with torch.cuda.stream(streams[g]):
+                    if graphs[g] is None:
+                        with _ws_slot(sts[g].slot):
+                            self._decode_step(sts[g])
+                    elif not (g == 0 and sampled_step is not None and sampled_step(step, sts[0])):
+                        graphs[g].replay()
+            if on_step is not None:
+                on_step(sts[0])
+            if eos_on and step % EOS_CHECK_EVERY == 0:
+                still = []
+                for g in live:
+                    if still and not retire:
+                        break                                  # one unfinished state keeps all of them stepping: the others need not be read
+                    with torch.cuda.stream(streams[g]):
+                        if not bool(sts[g].finished.all().item()):
+                            still.append(g)
+                if not still:
+                    break
+                if retire:
+                    live = still
+        if side_streams:
+            for sg in streams:
+                main.wait_stream(sg)
 
     def _generate(self, embeds: torch.Tensor, max_new_tokens: int, eos_token_id: Optional[int] = None,
                   pad_token_id: Optional[int] = None, min_new_tokens: int = 0, prefill_chunk: int = 0, use_graph: bool = True,
@@ -1152,66 +1240,30 @@ class GenerationEngine:
             if return_hidden:
                 hiddens.append(st.hn.clone())
 
-        main = torch.cuda.current_stream()
-        sts, graphs, streams = [], [], []
+        def sampled_step(step, st):
+            # roofline sampling (bench.py): this step runs the same launches eagerly with HIP events around the decode-attention kernel
+            prof = ops.PROFILER
+            if prof is None or not prof.decode_every or step % prof.decode_every != prof.decode_every // 2:
+                return False
+            with _ws_slot(st.slot):
+                prof.decode_eager, prof.decode_ctx = True, S + step
+                self._decode_step(st)
+                prof.decode_eager = False
+            return True
+
+        sts = []
         for g in range(G):
-            b0, b1 = B * g // G, B * (g + 1) // G
-            ops.WS_SLOT = g
-            sts.append(self._start(embeds[b0:b1], max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, prefill_chunk,
-                                   return_hidden, g, sink, sampling))
+            with _ws_slot(g):
+                sts.append(self._start(embeds[B * g // G:B * (g + 1) // G], max_new_tokens, eos_token_id, pad_token_id, min_new_tokens,
+                                       prefill_chunk, return_hidden, g, sink, sampling))
         if ops.PROFILER is not None:
             ops.PROFILER.mark("prefill_end")
-        # ---- decode loop: HIP graph replay, no host sync inside
-        for g, st in enumerate(sts):
-            ops.WS_SLOT = g
-            graphs.append(self._capture(st) if graphed else None)
-            streams.append(torch.cuda.Stream() if G > 1 else main)
-        ops.WS_SLOT = 0
-        if G > 1:
-            for sg in streams:
-                sg.wait_stream(main)
-        eos_on = sts[0].eos >= 0
-        check_every = 16
-        for step in range(1, max_new_tokens):
-            prof = ops.PROFILER
-            sample = graphed and prof is not None and prof.decode_every and step % prof.decode_every == prof.decode_every // 2
-            for g, st in enumerate(sts):
-                with torch.cuda.stream(streams[g]):
-                    if sample and g == 0:
-                        # roofline sampling (bench.py): this step runs the same launches eagerly with HIP events around the
-                        # decode-attention kernel; state is device-resident, so graph replays continue seamlessly after it
-                        ops.WS_SLOT = g
-                        prof.decode_eager, prof.decode_ctx = True, S + step
-                        self._decode_step(st)
-                        prof.decode_eager = False
-                        ops.WS_SLOT = 0
-                    elif graphs[g] is not None:
-                        graphs[g].replay()
-                    else:
-                        self._decode_step(st)
-            sink(sts[0])
-            if eos_on and step % check_every == 0:
-                done = True
-                for g, st in enumerate(sts):
-                    with torch.cuda.stream(streams[g]):
-                        done = done and bool(st.finished.all().item())
-                if done:
-                    break
-        if G > 1:
-            for sg in streams:
-                main.wait_stream(sg)
+        # the groups are ONE call: all of them step until all have finished (a retired group's buffer would hold the fill value, not its pad id)
+        self._run_steps(sts, max_new_tokens, graphed, G > 1, False, sink, sampled_step)
         if ops.PROFILER is not None:
             ops.PROFILER.mark("decode_end")
         n_done = int(sts[0].step_dev.item())
-        out_ids = sts[0].out_ids if G == 1 else torch.cat([st.out_ids for st in sts], 0)
-        out = out_ids[:, :n_done]
-        if eos_on:
-            # HF stops as soon as every row has finished: trim trailing all-pad columns produced between checks
-            fin_cols = (out_ids[:, :n_done] == sts[0].eos).int().cumsum(1) > 0
-            all_fin = fin_cols.all(0)
-            idx = torch.nonzero(all_fin)
-            if idx.numel():
-                out = out_ids[:, : int(idx[0].item()) + 1]
+        out = _trim_at_eos(sts[0].out_ids if G == 1 else torch.cat([st.out_ids for st in sts], 0), n_done, sts[0].eos)
         # st.out_ids is the persistent, graph-baked buffer the next generate() refills: hand the caller its own tensor (HF
         # generate returns fresh tensors; a caller that collects results over batches must not see them overwritten)
         res = [out.clone()]
@@ -1230,8 +1282,8 @@ class GenerationEngine:
                       return_step_logits: bool = False, return_hidden: bool = False, kv_cache_dtype: Optional[str] = None,
                       weight_dtype: Optional[str] = None):
         """kv_cache_dtype / weight_dtype: "bf16" / "fp8_e4m3" for this call (None: the engine's); see _generate_many for the rest."""
-        return self._with_modes(kv_cache_dtype, weight_dtype, self._retry_after_eviction, self._generate_many, embeds_list, max_new_tokens, eos_token_id, pad_token_id,
-                                  min_new_tokens, use_graph, sampling, return_first_logits, coalesce, max_rows, return_step_logits, return_hidden)
+        return self._call(kv_cache_dtype, weight_dtype, self._generate_many, embeds_list, max_new_tokens, eos_token_id, pad_token_id,
+                          min_new_tokens, use_graph, sampling, return_first_logits, coalesce, max_rows, return_step_logits, return_hidden)
 
     def _generate_many(self, embeds_list: List[torch.Tensor], max_new_tokens: int, eos_token_id: Optional[int] = None,
                        pad_token_id: Optional[int] = None, min_new_tokens: int = 0, use_graph: bool = True, sampling=None,
@@ -1266,68 +1318,29 @@ class GenerationEngine:
             return self._generate_coalesced(embeds_list, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling,
                                             return_first_logits, max_rows, return_step_logits, return_hidden)
         if G == 1:
-            r = self.generate(embeds_list[0], max_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id, min_new_tokens=min_new_tokens,
-                              use_graph=use_graph, sampling=sampling, return_first_logits=return_first_logits)
-            return [r]
+            return [self._generate(embeds_list[0], max_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id, min_new_tokens=min_new_tokens,
+                                   use_graph=use_graph, sampling=sampling, return_first_logits=return_first_logits)]
         need = sum(e.shape[0] * self.bytes_per_sequence(e.shape[1], max_new_tokens) for e in embeds_list) + self.fixed_bytes(max(e.shape[0] for e in embeds_list),
                                                                                                                             max(e.shape[1] for e in embeds_list))
         budget = self.memory_budget(0, 0, slots=G)
         if need > 0.94 * budget:
             raise MemoryError(f"generate_many: {G} batches need {need / 2**30:.1f} GiB of KV cache and scratch, {budget / 2**30:.1f} GiB available: put fewer in flight")
-        graphed = use_graph and max_new_tokens > 2
         firsts = []
 
         def sink(st):
             if return_first_logits:
                 firsts.append(st.logits.clone())
 
-        main = torch.cuda.current_stream()
-        sts, graphs, streams = [], [], []
         self._rope_tab(max(_round_up(e.shape[1] + max_new_tokens, 64) for e in embeds_list))    # grown ONCE: every group's launches bake its pointer
-        try:
-            for g, emb in enumerate(embeds_list):
-                ops.WS_SLOT = g
+        sts = []
+        for g, emb in enumerate(embeds_list):
+            with _ws_slot(g):
                 sts.append(self._start(emb, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, 0, False, g, sink, sampling))
-            for g, st in enumerate(sts):
-                ops.WS_SLOT = g
-                graphs.append(self._capture(st) if graphed else None)
-                streams.append(torch.cuda.Stream())
-        finally:
-            ops.WS_SLOT = 0
-        for sg in streams:
-            sg.wait_stream(main)
-        eos_on = sts[0].eos >= 0
-        live = list(range(G))
-        for step in range(1, max_new_tokens):
-            for g in live:
-                with torch.cuda.stream(streams[g]):
-                    ops.WS_SLOT = g
-                    if graphs[g] is not None:
-                        graphs[g].replay()
-                    else:
-                        self._decode_step(sts[g])
-            ops.WS_SLOT = 0
-            if eos_on and step % 16 == 0:
-                still = []
-                for g in live:
-                    with torch.cuda.stream(streams[g]):
-                        if not bool(sts[g].finished.all().item()):
-                            still.append(g)
-                live = still                                   # a batch whose rows have all finished stops stepping (HF stops that call)
-                if not live:
-                    break
-        for sg in streams:
-            main.wait_stream(sg)
+        self._run_steps(sts, max_new_tokens, use_graph and max_new_tokens > 2, True, True)
         outs = []
         for g, st in enumerate(sts):
-            n_done = int(st.step_dev.item())
-            out = st.out_ids[:, :n_done]
-            if eos_on:
-                fin_cols = (out == st.eos).int().cumsum(1) > 0
-                idx = torch.nonzero(fin_cols.all(0))
-                if idx.numel():
-                    out = st.out_ids[:, : int(idx[0].item()) + 1]
-            outs.append((out.clone(), firsts[g]) if return_first_logits else out.clone())
+            out = _trim_at_eos(st.out_ids, int(st.step_dev.item()), st.eos).clone()
+            outs.append((out, firsts[g]) if return_first_logits else out)
         return outs
 
     def _generate_coalesced(self, embeds_list, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling,
@@ -1340,27 +1353,15 @@ class GenerationEngine:
         per = self.bytes_per_sequence(Smax, max_new_tokens)
         budget = self.memory_budget(0, 0, slots=1)
         fit = (int(0.94 * budget) - self.fixed_bytes(min(sum(Bs), cap), Smax)) // per
-        cap = max(1, min(cap, fit))
-        total = sum(Bs)
-        n_waves = max(1, -(-total // cap))
-        target = -(-total // n_waves)                          # even waves: 60 batches of 8 at cap 448 run as 240 + 240, not 448 + 32
-        waves, cur, rows = [], [], 0
-        for g, b in enumerate(Bs):
-            if cur and rows + b > min(cap, max(target, b)):
-                waves.append(cur)
-                cur, rows = [], 0
-            cur.append(g)
-            rows += b
-        if cur:
-            waves.append(cur)
-        plan = {"B": total, "groups": [sum(Bs[g] for g in w) for w in waves], "bytes_per_seq": per, "budget": budget, "coalesced": True}
+        waves = _pack_waves(Bs, max(1, min(cap, fit)))
+        plan = {"B": sum(Bs), "groups": [sum(Bs[g] for g in w) for w in waves], "bytes_per_seq": per, "budget": budget, "coalesced": True}
         outs = [None] * len(embeds_list)
         for w in waves:
-            if len(w) == 1:                                    # a lone batch (or one larger than the cap: generate() plans its own split)
+            if len(w) == 1:                                    # a lone batch (or one larger than the cap: _generate plans its own split)
                 g = w[0]
-                outs[g] = self.generate(embeds_list[g], max_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
-                                        min_new_tokens=min_new_tokens, use_graph=use_graph, sampling=sampling, return_first_logits=return_first_logits,
-                                        return_step_logits=return_step_logits, return_hidden=return_hidden)
+                outs[g] = self._generate(embeds_list[g], max_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
+                                         min_new_tokens=min_new_tokens, use_graph=use_graph, sampling=sampling, return_first_logits=return_first_logits,
+                                         return_step_logits=return_step_logits, return_hidden=return_hidden)
                 continue
             res = self._ragged_wave([embeds_list[g] for g in w], max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling,
                                     return_first_logits, return_step_logits, return_hidden)
@@ -1381,21 +1382,12 @@ class GenerationEngine:
             if return_hidden:
                 steps.append(st.hn.clone())
 
-        ops.WS_SLOT = 0
-        st = self._start_ragged(embeds_list, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, sink, sampling, return_hidden)
+        with _ws_slot(0):
+            st = self._start_ragged(embeds_list, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, sink, sampling, return_hidden)
         if ops.PROFILER is not None:
             ops.PROFILER.mark("prefill_end")
-        graph = self._capture(st) if (use_graph and max_new_tokens > 2) else None
-        eos_on = st.eos >= 0
-        for step in range(1, max_new_tokens):
-            if graph is not None:
-                graph.replay()
-            else:
-                self._decode_step(st)
-            if return_step_logits or return_hidden:
-                sink(st)
-            if eos_on and step % 16 == 0 and bool(st.finished.all().item()):
-                break
+        self._run_steps([st], max_new_tokens, use_graph and max_new_tokens > 2, False, True,
+                        sink if (return_step_logits or return_hidden) else None)
         if ops.PROFILER is not None:
             ops.PROFILER.mark("decode_end")
         n_done = int(st.step_dev.item())
@@ -1403,17 +1395,12 @@ class GenerationEngine:
         outs, r0 = [], 0
         for e in embeds_list:
             r1 = r0 + int(e.shape[0])
-            out = st.out_ids[r0:r1, :n_done]
-            if eos_on:
-                # what this batch's own generate() call returns: HF stops a call as soon as all of ITS rows have finished
-                fin_cols = (out == st.eos).int().cumsum(1) > 0
-                idx = torch.nonzero(fin_cols.all(0))
-                if idx.numel():
-                    out = st.out_ids[r0:r1, : int(idx[0].item()) + 1]
+            # what this batch's own generate() call returns: HF stops a call as soon as all of ITS rows have finished
+            out = _trim_at_eos(st.out_ids[r0:r1], n_done, st.eos).clone()
             if return_step_logits or return_hidden:
-                outs.append((out.clone(), sl[r0:r1, : out.shape[1]].clone()))
+                outs.append((out, sl[r0:r1, : out.shape[1]].clone()))
             else:
-                outs.append((out.clone(), firsts[0][r0:r1].clone()) if return_first_logits else out.clone())
+                outs.append((out, firsts[0][r0:r1].clone()) if return_first_logits else out)
             r0 = r1
         return outs
 
@@ -1432,10 +1419,10 @@ class GenerationEngine:
         for n in groups:
             self.kv_budget_bytes = 1 << 62                    # the group sizes are decided: no re-planning inside
             try:
-                r = self.generate(embeds[b0:b0 + n], max_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
-                                  min_new_tokens=min_new_tokens, prefill_chunk=prefill_chunk, use_graph=use_graph,
-                                  return_step_logits=return_step_logits, return_hidden=return_hidden, return_first_logits=return_first_logits,
-                                  sampling=None if sampling is None else (sampling[0], sampling[1], sampling[2], sampling[3] + 104729 * b0))
+                r = self._generate(embeds[b0:b0 + n], max_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
+                                   min_new_tokens=min_new_tokens, prefill_chunk=prefill_chunk, use_graph=use_graph,
+                                   return_step_logits=return_step_logits, return_hidden=return_hidden, return_first_logits=return_first_logits,
+                                   sampling=None if sampling is None else (sampling[0], sampling[1], sampling[2], sampling[3] + 104729 * b0))
             finally:
                 self.kv_budget_bytes = saved
             parts.append(r if isinstance(r, tuple) else (r,))

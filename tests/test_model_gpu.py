@@ -1181,6 +1181,41 @@ def test_generate_many_refuses_batches_that_do_not_fit_together_and_returns_firs
     assert eng.generate_many([], 5) == []
 
 
+def test_decode_streams_with_no_pad_id_keep_every_group_stepping_until_all_have_finished():
+    """generate(decode_streams=2) with pad_token_id=None (a finished row emits the EOS id) == generate(decode_streams=1).  Row 0 finishes at its
+    4th token; the call crosses the EOS checks at steps 16 and 32 while the other group is still live.  The groups are ONE call: group 0 keeps
+    stepping (and writing EOS ids) until every group has finished - retired at the check, its buffer would keep the 0 it was pre-filled with."""
+    meta, A = load_fixture("full_tiny_llama")
+    model = build_tiny_crab(meta)
+    model.load_state_dict(weights_from_table(meta), strict=False)
+    eng = model.base_model.model._engine
+    emb = A["embeds_bs2"].cuda().to(BF)
+    eos = int(A["ids_bs2"][0, 3])
+    one = eng.generate(emb, 40, eos_token_id=eos, pad_token_id=None, decode_streams=1)
+    two = eng.generate(emb, 40, eos_token_id=eos, pad_token_id=None, decode_streams=2)
+    assert two.shape == one.shape and torch.equal(two, one), (two.tolist(), one.tolist())
+
+
+def test_generate_many_at_engine_level_graphed_and_eager_equal_separate_generate_calls():
+    """Engine level, with an EOS that retires the one-row batches at the first check while the two-row batch goes on: generate_many replayed
+    from graphs == generate_many stepped eagerly == three separate generate() calls, ids and lengths."""
+    meta, A = load_fixture("full_tiny_llama")
+    model = build_tiny_crab(meta)
+    model.load_state_dict(weights_from_table(meta), strict=False)
+    eng = model.base_model.model._engine
+    e1 = A["embeds_bs2"][:1].cuda().to(BF)
+    e2 = A["embeds_bs2"].cuda().to(BF)
+    eos = int(A["ids_bs2"][0, 3])
+    kw = dict(eos_token_id=eos, pad_token_id=2)
+    graphed = eng.generate_many([e1, e2, e1], 40, use_graph=True, **kw)
+    eager = eng.generate_many([e1, e2, e1], 40, use_graph=False, **kw)
+    assert len(graphed) == len(eager) == 3
+    for emb, a, b in zip([e1, e2, e1], graphed, eager):
+        solo = eng.generate(emb, 40, **kw)
+        assert a.shape == b.shape == solo.shape and torch.equal(a, b) and torch.equal(a, solo), (a.tolist(), b.tolist(), solo.tolist())
+    assert graphed[0].shape[1] == 4 and torch.equal(graphed[0].cpu(), A["ids_bs1"][:, :4])
+
+
 def _coalesce_setup(fixture="full_tiny_llama"):
     meta, A = load_fixture(fixture)
     model = build_tiny_crab(meta)
