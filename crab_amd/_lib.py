@@ -164,6 +164,9 @@ SYMBOLS = {
     "crab_rowfin_lora_ok": (_i, [_i, _i, _i]),
     "crab_attn_decode_rope_workspace": (_i64, [_i, _i, _i]),
     "crab_attn_decode_rope": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp, _f, _vp, _i64]),
+    "crab_attn_prefix_workspace": (_i64, [_i, _i, _i]),
+    "crab_attn_prefix_partial": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _f]),
+    "crab_attn_own_merge": (_i, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _vp, _f, _vp]),
     "crab_hyperlora_mix": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _i64, _i, _i, _i, _i, _i, _f]),
     "crab_hyperlora_route_workspace": (_i64, [_i, _i, _i]),
     "crab_hyperlora_route": (_i, [_vp, _vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, _vp, _i64, _i, _f, _vp, _i64]),

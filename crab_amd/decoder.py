@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import contextlib
 import math
+import types
 from dataclasses import dataclass
 from typing import List, Optional
 
@@ -217,6 +218,7 @@ class GenerationEngine:
         self._ws = {}
         self._kv = {}
         self._dec = {}                 # slot -> persistent decode state (+ captured graph)
+        self._prefix = None            # generate_shared_prefix: the persistent buffers of the last wave shape (_shared_prefix_buffers: two _SharedPrefix forms)
         self._attn_ws = {}             # B -> scratch of the fused small-batch attention for calls that run in the SHARED prefill workspace (_attn_scratch)
         self.kv_budget_bytes = None    # None: ask the device (hipMemGetInfo); an int caps what generate() may plan with (tests)
         self.last_plan = None          # what the last generate() decided: {"B", "groups", "bytes_per_seq", "budget"}
@@ -319,6 +321,7 @@ class GenerationEngine:
         self._ws = {}
         self._kv = {}
         self._attn_ws = {}
+        self._prefix = None
         self._table = None
         self._table8 = None
         for l in self.model.layers:                 # the FP8 forms of the packed weights (weight_dtype = "fp8_e4m3"): rebuilt on the next use
@@ -474,6 +477,9 @@ class GenerationEngine:
         free, _total = torch.cuda.mem_get_info(self.device)
         cached = torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)
         own = sum(t.numel() * t.element_size() for bufs in self._kv.values() for t in bufs)
+        px = getattr(self, "_prefix", None)                    # the shared-prefix buffers of an earlier wave shape are replaced, not kept beside the new ones
+        if px is not None:
+            own += sum(t.numel() * t.element_size() for t in (px.decode.pk, px.decode.pv, px.decode.ws))
         return int(free + cached + own)
 
     def _evict_for(self, need_bytes: int, slot: int, slack: int = 4 << 30) -> bool:
@@ -626,7 +632,7 @@ class GenerationEngine:
     def _layers(self, ws: _Workspace, B: int, S: int, kc: torch.Tensor, vc: torch.Tensor, b0: int, Tmax: int, pos0: int,
                 pos_dev: Optional[torch.Tensor], vt: Optional[torch.Tensor], pos_ids: Optional[torch.Tensor] = None,
                 kv_start: Optional[torch.Tensor] = None, key_mask: Optional[torch.Tensor] = None, t0: int = 0,
-                row_off: Optional[torch.Tensor] = None, last_rows: bool = False, kv_scales=None, w8: bool = False):
+                row_off: Optional[torch.Tensor] = None, last_rows: bool = False, kv_scales=None, w8: bool = False, prefix=None):
         """x (ws.x[:B*S]) -> x after all layers.  w8 (decode steps of generate() only, <= 16 rows): the projections stream the FP8 weights.  Prefill when vt is given (S rows per sequence, positions pos0..),
         decode otherwise (S == 1, position read from pos_dev).  kc/vc: [L, Btot, Hk, Tmax, d]; rows b0..b0+B.
         The RAGGED decode batch (generate_many(coalesce=True)): sequences of different prompt lengths are right-aligned in one cache - a
@@ -640,7 +646,13 @@ class GenerationEngine:
         visibility bit per key (any other mask); they select the per-launch sequence below (RoPE as its own pass), which is not the
         benchmarked path.
         kv_scales = (k_scale, v_scale) fp32 [L, Btot, Hk, Tmax]: kc / vc are the uint8 codes of the FP8 KV cache (decode steps only): the
-        projection leaves its raw row and crab_attn_decode_fp8 rotates, quantises, appends and attends (row_off = its first visible key)."""
+        projection leaves its raw row and crab_attn_decode_fp8 rotates, quantises, appends and attends (row_off = its first visible key).
+        prefix (_SharedPrefix; generate_shared_prefix): the B rows are questions about prefix.pk.shape[1] clips whose first prefix.P positions live
+        once per clip in prefix.pk / prefix.pv [L, C, Hk, Tp, d]; kc / vc hold the rows' own keys only.  Per-launch sequence; the attention is
+        crab_attn_prefix_partial + crab_attn_own_merge.  Decode step (vt None, S == 1): row_off = first own slot of every row (the first visible
+        key), prefix.rope_off = that minus P (the rotary offset: slot - rope_off = position, a NEGATIVE word - crab_qkv_rope_split_ragged only
+        subtracts it).  Suffix prefill (vt None, S > 1): pos_ids = the rotary positions, kv_start = the first own slot; query s sees the own
+        slots kv_start[b] .. pos0 + s."""
         c = self.cfg
         H, Hk, d = c.num_attention_heads, c.num_key_value_heads, c.head_dim
         M = B * S
@@ -653,15 +665,22 @@ class GenerationEngine:
                 raise NotImplementedError('kv_cache_dtype="fp8_e4m3": the masked one-token step of forward() (position_ids / attention_mask; crab_attn_decode_keymask) has no fp8 form')
             if kc.dtype != torch.uint8 or not (kc.is_contiguous() and vc.is_contiguous() and kv_scales[0].is_contiguous() and kv_scales[1].is_contiguous()):
                 raise ValueError("fp8 KV cache: contiguous uint8 codes and fp32 scales expected")
+        if prefix is not None:
+            if kv_scales is not None or self._fp8:
+                raise NotImplementedError('kv_cache_dtype="fp8_e4m3" with a shared prefix (generate_shared_prefix) is not implemented: the prefix cache and its attention kernels are bf16')
+            if w8:
+                raise NotImplementedError('weight_dtype="fp8_e4m3" with a shared prefix (generate_shared_prefix) is not implemented')
+            if vt is not None or key_mask is not None or t0 or b0 or last_rows or (S == 1) != (row_off is not None) or (S > 1) != (pos_ids is not None and kv_start is not None):
+                raise ValueError("prefix=: a decode step takes row_off, the suffix prefill pos_ids and kv_start; rows 0 .. B - 1, no V^T, no key mask")
         x, h, qkv, att, act = ws.x[:M], ws.h[:M], ws.qkv[:M], ws.att[:M], ws.act[:M]
-        tab = self._rope_tab(Tmax)
+        tab = self._rope_tab(Tmax if prefix is None else prefix.P + Tmax)
         scale = 1.0 / math.sqrt(d)
         ldq = qkv.stride(0)
         layers = self.model.layers
         ops.rmsnorm(x, layers[0].input_layernorm.weight, c.rms_norm_eps, out=h)
         timed = ops.per_launch_profiling() and not torch.cuda.is_current_stream_capturing()
         masked = pos_ids is not None or kv_start is not None or key_mask is not None
-        if row_off is not None and (vt is not None or masked):
+        if row_off is not None and (vt is not None or masked) and prefix is None:
             raise ValueError("row_off is a decode-step argument (no masks / position ids next to it)")
         contig = kc.is_contiguous() and vc.is_contiguous()
         # the native sequencer takes a prefill's rotary positions / first visible keys as well (crab_llama_io.pos_ids / kv_start); a general key
@@ -673,12 +692,12 @@ class GenerationEngine:
         native_ok = key_mask is None and (not masked or (vt is not None and pos_dev is None and
                                                          (pos_ids is None or (pos_ids.dtype == torch.int32 and pos_ids.stride(1) == 1))))
         last_rows = bool(last_rows) and vt is not None and S > 1 and key_mask is None and pos_dev is None
-        if NATIVE_LAYERS and not timed and native_ok and contig and (vt is not None or S == 1):
+        if prefix is None and NATIVE_LAYERS and not timed and native_ok and contig and (vt is not None or S == 1):
             self._layers_native(ws, B, S, kc, vc, b0, Tmax, pos0, pos_dev, vt, t0, row_off, pos_ids, kv_start, last_rows, kv_scales, w8)
             return x, h
         u_qkv = None                                   # router output for the q|k|v group when a producer epilogue made it
         # small batch: the projection leaves its raw row, ONE launch does RoPE + KV append + split-context attention (as csrc/llama_layer.hip)
-        aw = self._attn_scratch(ws, B) if (vt is None and S == 1 and not masked and row_off is None and contig and kv_scales is None) else None
+        aw = self._attn_scratch(ws, B) if (vt is None and S == 1 and not masked and row_off is None and contig and kv_scales is None and prefix is None) else None
         fuse_attn = aw is not None and aw.numel() >= ops.attn_decode_rope_bytes(B, H, d)
         for li, layer in enumerate(layers):
             a, m = layer.self_attn, layer.mlp
@@ -689,7 +708,12 @@ class GenerationEngine:
             if last_rows and li + 1 == len(layers):
                 self._last_layer_last_rows(ws, layer, B, S, kcl, vcl, lcontig, Tmax, pos0, vt, pos_ids, kv_start, u_qkv)
                 return x, h
-            if fuse_attn or kv_scales is not None:
+            if prefix is not None:
+                # RoPE + KV append as their own pass: the rotary offset (prefix.rope_off) is not the first visible key (row_off) here
+                a._qkv(h, out=qkv, t_buf=ws.t, u_buf=ws.u, u_ready=u_qkv)
+                ops.qkv_rope_split(qkv, tab, kcl, vcl, None, B, S, H, Hk, d, Tmax, pos0=pos0, pos_dev=pos_dev, pos_ids=pos_ids,
+                                   row_off=prefix.rope_off if S == 1 else None)
+            elif fuse_attn or kv_scales is not None:
                 a._qkv(h, out=qkv, t_buf=ws.t, u_buf=ws.u, u_ready=u_qkv, fp8=w8)
             elif vt is None and S == 1 and lcontig and not masked:
                 # decode: RoPE + KV append ride on the q|k|v projection (fused into its split-K reduction when it has one)
@@ -708,7 +732,11 @@ class GenerationEngine:
             else:
                 a._qkv(h, out=qkv, t_buf=ws.t, u_buf=ws.u, u_ready=u_qkv, fp8=w8)
                 ops.qkv_rope_split(qkv, tab, kcl, vcl, vt, B, S, H, Hk, d, Tmax, pos0=pos0, pos_dev=pos_dev, pos_ids=pos_ids, row_off=row_off)
-            if vt is not None:
+            if prefix is not None:
+                ops.attn_prefix_partial(qkv, prefix.pk[li], prefix.pv[li], prefix.ws, prefix.tile_rows, prefix.row_clip, M, H, Hk, d, prefix.P, scale)
+                ops.attn_own_merge(qkv, prefix.ws, kcl, vcl, att, B, S, H, Hk, d, Tmax, pos0 + 1, scale, ctx_dev=pos_dev,
+                                   kv_start=row_off if S == 1 else kv_start)
+            elif vt is not None:
                 Sp = vt.shape[-1]
                 ops.attn_fwd(qkv, kcl, vt, att, q_strides=(S * ldq, d, ldq), k_strides=(Hk * Tmax * d, Tmax * d, d),
                              vt_strides=(Hk * d * Sp, d * Sp, Sp), o_strides=(S * H * d, H * d), B=B, H=H, Hk=Hk, Sq=S,
@@ -779,11 +807,12 @@ class GenerationEngine:
     def prefill(self, embeds: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, b0: int = 0, all_logits: bool = False,
                 logits_out: Optional[torch.Tensor] = None, hn_out: Optional[torch.Tensor] = None,
                 pos_ids: Optional[torch.Tensor] = None, kv_start: Optional[torch.Tensor] = None, key_mask: Optional[torch.Tensor] = None,
-                t0: int = 0):
+                t0: int = 0, want_logits: bool = True):
         """embeds [B,S,D] bf16 -> (fp32 logits, post-final-norm hidden) of the LAST row ([B,V], [B,D]), or of all
         rows with all_logits ([B,S,V], [B,S,D]); fills cache rows b0..b0+B.  The reference computes lm_head on all
         S rows and discards S-1 of them (modeling_llama.py:1260); generate() only needs the last row
-        (SURVEY.md appendix A.2)."""
+        (SURVEY.md appendix A.2).  want_logits = False (last-row form only): the caller wants the cache alone (the shared prefix of
+        generate_shared_prefix) - no lm_head product, logits is None."""
         c = self.cfg
         B, S, D = embeds.shape
         Tmax = kc.shape[3]
@@ -801,7 +830,7 @@ class GenerationEngine:
         if last_rows:
             hn = hn_out if hn_out is not None else torch.empty((B, D), device=self.device, dtype=BF16)
             ops.copy_rows(hfin, hn, B, D)
-            logits = ops.gemm(hn, self.lm_head.weight, out=logits_out, out_fp32=True)
+            logits = ops.gemm(hn, self.lm_head.weight, out=logits_out, out_fp32=True) if want_logits else None
             return logits, hn
         if all_logits:
             hn = hfin.clone()
@@ -809,7 +838,7 @@ class GenerationEngine:
             return logits.view(B, S, -1), hn.view(B, S, D)
         hn = hn_out if hn_out is not None else torch.empty((B, D), device=self.device, dtype=BF16)
         ops.copy_rows(hfin[S - 1:], hn, B, D, lds=S * D)                  # hn[b] = hfin[b*S + S-1]
-        logits = ops.gemm(hn, self.lm_head.weight, out=logits_out, out_fp32=True)
+        logits = ops.gemm(hn, self.lm_head.weight, out=logits_out, out_fp32=True) if want_logits else None
         return logits, hn
 
     # ------------------------------------------------------------------ teacher-forced scoring
@@ -954,7 +983,7 @@ class GenerationEngine:
         ws = st.ws
         ops.embedding(st.cur_ids, self.model.embed_tokens.weight, out=ws.x[:B])
         x, hfin = self._layers(ws, B, 1, st.kc, st.vc, 0, st.Tmax, 0, st.pos_dev, None, row_off=st.row_off,
-                               kv_scales=(st.ks, st.vs) if st.ks is not None else None, w8=st.w8)
+                               kv_scales=(st.ks, st.vs) if st.ks is not None else None, w8=st.w8, prefix=st.prefix)
         ops.gemm(hfin, self.lm_head.weight, out=st.logits)
         if st.want_hidden:
             ops.copy_rows(hfin, st.hn, B, hfin.shape[1])
@@ -971,11 +1000,12 @@ class GenerationEngine:
             ops.sample_select(st.logits, st.cur_ids, st.out_ids, st.step_dev, st.finished, st.eos, st.pad, st.min_new, t, k, p_, seed + 7919 * st.slot)
 
     def _state(self, B: int, S: int, max_new_tokens: int, eos_token_id, pad_token_id, min_new_tokens: int, return_hidden: bool, slot: int,
-               sampling=None, ragged: bool = False) -> "_DecodeState":
+               sampling=None, ragged: bool = False, extra_key=()) -> "_DecodeState":
         """The persistent decode state of `slot` for B sequences whose (longest) prompt has S rows: KV cache, per-row words, logits and the HIP
         graph captured over them.  Kept per slot and reused by every call whose shapes, flags and buffers are the same: the key holds
         everything the captured launches bake in (pointers included).  ragged: the state of a coalesced batch (generate_many(coalesce=True)) -
-        it owns a row_off word per row (first cache slot of the row's sequence) that the captured decode step reads."""
+        it owns a row_off word per row (first cache slot of the row's sequence) that the captured decode step reads.  extra_key: what else a caller's captured step bakes in
+        (generate_shared_prefix: the prefix cache, its length, the tile plan and the workspace)."""
         if int(max_new_tokens) < 1:                             # HF: GenerationConfig.validate() - "`max_new_tokens` must be greater than 0"; here the first token's slot would not exist
             raise ValueError(f"`max_new_tokens` must be greater than 0, but is {max_new_tokens}.")
         dev = self.device
@@ -1002,7 +1032,7 @@ class GenerationEngine:
                tab.data_ptr(), self.lm_head.weight.data_ptr(), self.model.embed_tokens.weight.data_ptr(),
                self.model.layers[0].self_attn._qkv.W.data_ptr(),
                self.model.layers[0].self_attn._qkv.RA is not None, sampling, bool(ragged),
-               self._kv_mode, ks.data_ptr() if ks is not None else 0, vs.data_ptr() if vs is not None else 0, w8_key)
+               self._kv_mode, ks.data_ptr() if ks is not None else 0, vs.data_ptr() if vs is not None else 0, w8_key) + tuple(extra_key)
         st = self._dec.get(slot)
         if st is None or st.key != key:
             st = _DecodeState()
@@ -1020,6 +1050,7 @@ class GenerationEngine:
             st.row_off = torch.zeros((B,), device=dev, dtype=torch.int32) if ragged else None
             st.eos, st.pad, st.min_new, st.want_hidden = eos, pad, int(min_new_tokens), bool(return_hidden)
             st.sampling = sampling
+            st.prefix = None
             self._dec[slot] = st
         st.S = S
         st.cur_ids.zero_(); st.out_ids.fill_(pad_token_id if pad_token_id is not None else 0); st.finished.zero_()
@@ -1404,6 +1435,172 @@ class GenerationEngine:
             r0 = r1
         return outs
 
+    # ------------------------------------------------------------------ several questions per clip on one prefix KV
+    def shared_prefix_bytes(self, C: int, P: int, B: int, S: int, max_new_tokens: int) -> int:
+        """Device bytes of one generate_shared_prefix wave - the sibling of B * bytes_per_sequence(P + S, ...): the prefix rows are counted ONCE PER
+        CLIP (C x the KV bytes of round_up(P, 64) rows), every one of the B questions pays only for its own round_up(S + max_new_tokens, 64) cache
+        rows and its decode row, plus the fp32 partials of the prefix attention (B x S query rows in the suffix prefill) and the prefill scratch."""
+        c = self.cfg
+        partials = B * max(S, 1) * c.num_attention_heads * (c.head_dim + 2) * 4
+        return C * self.kv_bytes_per_sequence(_round_up(P, 64)) + B * self.bytes_per_sequence(S, max_new_tokens) + partials + \
+            max(self.fixed_bytes(C, P), self.fixed_bytes(B, S))
+
+    def plan_shared_prefix(self, Gs: List[int], P: int, S: int, max_new_tokens: int, max_rows: Optional[int] = None) -> List[List[int]]:
+        """plan_batch's sibling for generate_shared_prefix: the clips (Gs[c] questions each, prefix of P rows, longest question S rows), in order,
+        as waves of whole clips with at most min(max_rows, ops.DECODE_MAX_ROWS) rows that fit the memory budget (shared_prefix_bytes: the prefix
+        counted once per clip).  The row cap is halved until every wave fits; a single clip that does not fit raises MemoryError."""
+        cap = min(int(max_rows), ops.DECODE_MAX_ROWS) if max_rows else ops.DECODE_MAX_ROWS
+        # the questions of a wave are prefilled in ONE front-padded pass of rows x S rows: at most SUFFIX_PASS_ROWS of them (the row cap of a
+        # prefill chunk, plan_prefill_chunks), so long questions make smaller waves instead of being refused
+        cap = max(1, min(cap, SUFFIX_PASS_ROWS // max(int(S), 1)))
+        if max(Gs) > cap:
+            raise ValueError(f"generate_shared_prefix: a clip with {max(Gs)} questions of up to {S} rows exceeds the {cap} rows of a wave "
+                             f"({ops.DECODE_MAX_ROWS} per decode step, {SUFFIX_PASS_ROWS} rows per suffix prefill pass); split its questions")
+        budget = self.memory_budget(0, 0, slots=1)
+        while True:
+            waves = _pack_waves(list(Gs), cap)
+            need = max(self.shared_prefix_bytes(len(w), P, sum(Gs[c] for c in w), S, max_new_tokens) for w in waves)
+            if need <= 0.94 * budget:
+                break
+            if all(len(w) == 1 for w in waves):
+                raise MemoryError(f"generate_shared_prefix: one clip needs {need / 2**30:.1f} GiB, {budget / 2**30:.1f} GiB available")
+            cap = max(max(Gs), cap // 2)
+        self.last_plan = {"B": sum(Gs), "groups": [sum(Gs[c] for c in w) for w in waves], "bytes": need, "budget": budget, "shared_prefix": True}
+        return waves
+
+    def _shared_prefix_buffers(self, C: int, P: int, Gs: List[int], Smax: int):
+        """The persistent device side of a wave, kept while (C, P, Gs, Smax) repeat so that a captured decode step stays valid: prefix cache
+        [L, C, Hk, round_up(P, 64), d] x 2, the partials workspace, the per-row rotary offsets and the two tile plans (ops.prefix_tile_plan):
+        .decode - clip c owns Gs[c] consecutive query rows - and .prefill - Gs[c] * Smax rows (question-major)."""
+        c = self.cfg
+        L, H, Hk, d = c.num_hidden_layers, c.num_attention_heads, c.num_key_value_heads, c.head_dim
+        key = (C, P, tuple(Gs), Smax, str(self.device))
+        px = self._prefix
+        if px is None or px.shape_key != key:
+            self._prefix = px = None
+            dev, B = self.device, sum(Gs)
+            px = types.SimpleNamespace(shape_key=key)
+            shape = (L, C, Hk, _round_up(P, 64), d)
+            pk, pv = torch.empty(shape, device=dev, dtype=BF16), torch.empty(shape, device=dev, dtype=BF16)
+            ws = torch.empty((ops.attn_prefix_bytes(B * Smax, H, d),), device=dev, dtype=torch.uint8)
+            rope_off = torch.zeros((B,), device=dev, dtype=torch.int32)
+            forms = []
+            for rows in (list(Gs), [G * Smax for G in Gs]):
+                tiles, row_clip = ops.prefix_tile_plan(rows, H, Hk)
+                forms.append(_SharedPrefix(pk, pv, P, ws, rope_off, torch.tensor(tiles, dtype=torch.int32).reshape(-1).to(dev),
+                                           torch.tensor(row_clip, dtype=torch.int32).to(dev)))
+            px.decode, px.prefill = forms
+            # what a captured decode step bakes in beyond _state's own key
+            px.key = (P, tuple(Gs), pk.data_ptr(), pv.data_ptr(), ws.data_ptr(), rope_off.data_ptr(), px.decode.tile_rows.data_ptr(),
+                      px.decode.row_clip.data_ptr())
+            self._prefix = px
+        return px
+
+    @torch.no_grad()
+    def generate_shared_prefix(self, prefix_embeds: torch.Tensor, suffix_embeds, max_new_tokens: int, eos_token_id: Optional[int] = None,
+                               pad_token_id: Optional[int] = None, min_new_tokens: int = 0, use_graph: bool = True, sampling=None,
+                               return_first_logits: bool = False, return_step_logits: bool = False, kv_cache_dtype: Optional[str] = None,
+                               weight_dtype: Optional[str] = None, max_rows: Optional[int] = None):
+        """Several questions per clip on ONE prefix KV.  prefix_embeds [C, P, D] bf16: the shared part of C clips (everything up to the question
+        text; the same P for all).  suffix_embeds: C lists, one [S_cg, D] tensor per question of the clip.  Returns one id tensor per clip,
+        [G_c, n] (with return_first_logits (ids, fp32 [G_c, V]); with return_step_logits (ids, fp32 [G_c, n, V])): what
+        generate_many(coalesce=True) returns for the sequences cat(prefix_c, suffix_cg) - the same ragged batch, EOS trim (a clip stops once
+        all ITS questions have finished) and padding of finished rows - within the bf16 tolerance of the decoder (the softmax is summed in
+        another order), while the prefix is prefilled, stored and, per decode step and kv head, read once per clip instead of once per question.
+
+        Layout (shared_prefix_layout): the prefix goes through prefill() into its own cache [L, C, Hk, round_up(P, 64), d].  The B = sum G_c
+        questions are the rows of one ragged decode state whose cache holds ONLY their own keys: question b is right-aligned at Smax = max S, first
+        own slot Smax - S_b (the first visible key of the attention), rotary positions P + (slot - first slot) (the RoPE pass takes the offset
+        first slot - P, a negative word).  Rows of a clip are consecutive; the prefix attention (crab_attn_prefix_partial) runs on tiles of up
+        to 16 // (H // Hk) query rows of ONE clip: a clip's rows are cut into full tiles from its first row on and the remainder forms a partial
+        tile, so clips with different numbers of questions mix freely and no tile spans two clips (ops.prefix_tile_plan).
+        More rows than a decode step takes (ops.DECODE_MAX_ROWS, max_rows) or than fit the memory run as consecutive waves of whole clips
+        (plan_shared_prefix).  Sample mode draws per (seed, step, row of the wave), as the coalesced form does.
+        kv_cache_dtype = "fp8_e4m3" and weight_dtype = "fp8_e4m3" raise NotImplementedError: the shared prefix is a bf16 path."""
+        return self._call(kv_cache_dtype, weight_dtype, self._generate_shared_prefix, prefix_embeds, suffix_embeds, max_new_tokens, eos_token_id,
+                          pad_token_id, min_new_tokens, use_graph, sampling, return_first_logits, return_step_logits, max_rows)
+
+    def _generate_shared_prefix(self, prefix_embeds, suffix_embeds, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling,
+                                return_first_logits, return_step_logits, max_rows):
+        if self._fp8:
+            raise NotImplementedError('kv_cache_dtype="fp8_e4m3" with a shared prefix (generate_shared_prefix) is not implemented: the prefix cache and its attention kernels are bf16')
+        if getattr(self, "_w_mode", "bf16") == "fp8_e4m3":
+            raise NotImplementedError('weight_dtype="fp8_e4m3" with a shared prefix (generate_shared_prefix) is not implemented')
+        if return_first_logits and return_step_logits:
+            raise NotImplementedError("generate_shared_prefix: return_first_logits / return_step_logits one at a time")
+        if prefix_embeds.dim() != 3 or prefix_embeds.dtype != BF16 or prefix_embeds.shape[1] < 1:
+            raise ValueError("prefix_embeds must be a bf16 [C, P, D] tensor with P >= 1")
+        C, P, D = prefix_embeds.shape
+        if len(suffix_embeds) != C or any(len(qs) < 1 for qs in suffix_embeds) or \
+                any(q.dim() != 2 or q.shape[0] < 1 or q.shape[1] != D or q.dtype != BF16 for qs in suffix_embeds for q in qs):
+            raise ValueError("suffix_embeds must hold, per clip, a non-empty list of bf16 [S, D] tensors with S >= 1")
+        Gs = [len(qs) for qs in suffix_embeds]
+        Smax = max(int(q.shape[0]) for qs in suffix_embeds for q in qs)
+        outs = []
+        for w in self.plan_shared_prefix(Gs, P, Smax, max_new_tokens, max_rows):
+            outs += self._shared_prefix_wave(prefix_embeds[w[0]:w[-1] + 1], [suffix_embeds[c] for c in w], max_new_tokens, eos_token_id, pad_token_id,
+                                             min_new_tokens, use_graph, sampling, return_first_logits, return_step_logits)
+        return outs
+
+    def _shared_prefix_wave(self, prefix_embeds, suffix_embeds, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling,
+                            return_first_logits, return_step_logits):
+        C, P, D = prefix_embeds.shape
+        Gs = [len(qs) for qs in suffix_embeds]
+        flat = [q for qs in suffix_embeds for q in qs]
+        lay = shared_prefix_layout(P, [int(q.shape[0]) for q in flat], max_new_tokens)
+        B, Smax, Tmax = len(flat), lay["Smax"], lay["Tmax"]
+        assert B * Smax <= SUFFIX_PASS_ROWS, "plan_shared_prefix sizes the waves for one suffix prefill pass"
+        dev = self.device
+        self._rope_tab(P + Tmax)                               # grown before any launch bakes its pointer: positions run to P + Tmax
+        px = self._shared_prefix_buffers(C, P, Gs, Smax)
+        firsts, steps = [], []
+
+        def sink(st):
+            if return_first_logits and not firsts:
+                firsts.append(st.logits.clone())
+            if return_step_logits:
+                steps.append(st.logits.clone())
+
+        with _ws_slot(0):
+            # ---- the prefix: the existing prefill, once per clip (its last-row logits are not needed: no lm_head product)
+            b0 = 0
+            for n in self.plan_prefill_chunks(C, P):
+                self.prefill(prefix_embeds[b0:b0 + n], px.decode.pk, px.decode.pv, b0=b0, want_logits=False)
+                b0 += n
+            st = self._state(B, Smax, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, False, 0, sampling, ragged=True, extra_key=px.key)
+            st.prefix = px.decode
+            st.row_off.copy_(torch.tensor(lay["first_slot"], dtype=torch.int32))
+            px.decode.rope_off.copy_(torch.tensor(lay["rope_off"], dtype=torch.int32))
+            # ---- the questions: one front-padded pass of Smax rows per question over [prefix of the clip ; own keys up to the row's]
+            emb = torch.zeros((B, Smax, D), device=dev, dtype=BF16)
+            for b, q in enumerate(flat):
+                emb[b, Smax - q.shape[0]:] = q
+            M = B * Smax
+            ws = self._workspace(M)
+            ops.cast_rows(emb.reshape(M, D), ws.x, M, D)
+            if Smax == 1:                                      # one row per question: the decode form at slot 0
+                x, hfin = self._layers(ws, B, 1, st.kc, st.vc, 0, Tmax, 0, None, None, row_off=st.row_off, prefix=px.decode)
+            else:
+                pos_ids = torch.tensor(lay["pos_ids"], dtype=torch.int32).to(dev)
+                x, hfin = self._layers(ws, B, Smax, st.kc, st.vc, 0, Tmax, 0, None, None, pos_ids=pos_ids, kv_start=st.row_off, prefix=px.prefill)
+            ops.copy_rows(hfin[Smax - 1:], st.hn, B, D, lds=Smax * D)         # the last row of every question
+            ops.gemm(st.hn, self.lm_head.weight, out=st.logits, out_fp32=True)
+            del emb
+            self._first_token(st, sink)
+        self._run_steps([st], max_new_tokens, use_graph and max_new_tokens > 2, False, True, sink if return_step_logits else None)
+        n_done = int(st.step_dev.item())
+        sl = torch.stack(steps, 1) if return_step_logits else None
+        outs, r0 = [], 0
+        for G in Gs:
+            r1 = r0 + G
+            out = _trim_at_eos(st.out_ids[r0:r1], n_done, st.eos).clone()
+            if return_step_logits:
+                outs.append((out, sl[r0:r1, : out.shape[1]].clone()))
+            else:
+                outs.append((out, firsts[0][r0:r1].clone()) if return_first_logits else out)
+            r0 = r1
+        return outs
+
     def _generate_split(self, groups, embeds, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, prefill_chunk, use_graph,
                         return_step_logits, return_hidden, return_first_logits, sampling=None):
         """The batch does not fit the device's memory in one piece: generate the groups one after the other (rows are independent,
@@ -1470,8 +1667,35 @@ class _DecodeState:
     pass
 
 
+class _SharedPrefix:
+    """One form (decode step or suffix prefill) of a generate_shared_prefix wave as _layers(prefix=...) takes it: pk / pv - the prefix cache
+    [L, C, Hk, Tp, d]; P - live prefix rows; ws - the fp32 partials of crab_attn_prefix_partial (uint8); tile_rows / row_clip - the tile plan of the
+    form's query rows (ops.prefix_tile_plan, device int32); rope_off - int32 [B], first own slot - P (the decode step's rotary offset).  The two
+    forms of a wave share everything but the tile plan."""
+
+    def __init__(self, pk, pv, P, ws, rope_off, tile_rows, row_clip):
+        self.pk, self.pv, self.P, self.ws, self.rope_off, self.tile_rows, self.row_clip = pk, pv, P, ws, rope_off, tile_rows, row_clip
+
+
 def _round_up(a: int, b: int) -> int:
     return (a + b - 1) // b * b
+
+
+SUFFIX_PASS_ROWS = 32768       # rows of one suffix prefill pass of generate_shared_prefix (= the row cap of a prefill chunk)
+
+
+def shared_prefix_layout(P: int, suffix_lens: List[int], max_new_tokens: int) -> dict:
+    """Slots and positions of generate_shared_prefix (host arithmetic): question b of S_b rows is right-aligned at Smax = max S in an own cache of
+    Tmax = round_up(Smax + max_new_tokens, 64) slots.  first_slot[b] = Smax - S_b (first visible own key); the token in slot s >= first_slot[b]
+    sits at rotary position P + (s - first_slot[b]), i.e. s - rope_off[b] with rope_off[b] = first_slot[b] - P (negative whenever P exceeds the
+    padding); pos_ids[b][s] for the Smax prefill slots (padding slots, never visible, get a clamped valid position).  The token decoded at step
+    t lands in slot Smax + t - 1 of every row."""
+    if P < 1 or not suffix_lens or min(suffix_lens) < 1:
+        raise ValueError("shared_prefix_layout: P >= 1 and every question at least one row")
+    Smax = max(suffix_lens)
+    first = [Smax - S for S in suffix_lens]
+    return {"Smax": Smax, "Tmax": _round_up(Smax + max_new_tokens, 64), "first_slot": first, "rope_off": [f - P for f in first],
+            "pos_ids": [[max(P + s - f, 0) for s in range(Smax)] for f in first]}
 
 
 class ScoreOutput:

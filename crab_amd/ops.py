@@ -688,6 +688,75 @@ def _chk_i32(name: str, t: Optional[torch.Tensor], n: int, device):
         raise ValueError(f"{name} must be a contiguous int32 [{n}] tensor on {device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
 
 
+def prefix_tile_plan(rows_per_clip, H: int, Hk: int):
+    """The tiles of crab_attn_prefix_partial for a batch whose clip c owns rows_per_clip[c] CONSECUTIVE query rows (its questions in a decode step,
+    questions x suffix rows in the suffix prefill): -> (tiles, row_clip), tiles = [(first row, rows)], row_clip[row] = clip.  A tile takes at most
+    16 // (H // Hk) rows (every row brings its H // Hk heads of a kv head into the 16 operand rows) and never spans two clips: a clip's rows are
+    cut into full tiles from its first row on, and its last tile holds the remainder (a PARTIAL tile: fewer rows, the operand rows behind them zero)."""
+    if Hk <= 0 or H % Hk or not 1 <= H // Hk <= 16:
+        raise ValueError(f"prefix_tile_plan: H = {H}, Hk = {Hk}")
+    per = 16 // (H // Hk)
+    tiles, row_clip, r0 = [], [], 0
+    for c, R in enumerate(rows_per_clip):
+        R = int(R)
+        if R < 1:
+            raise ValueError("prefix_tile_plan: every clip needs at least one row")
+        tiles += [(r0 + t, min(per, R - t)) for t in range(0, R, per)]
+        row_clip += [c] * R
+        r0 += R
+    return tiles, row_clip
+
+
+def _chk_prefix_ws(name: str, ws, q, rows: int, H: int, d: int):
+    # the partials travel as a raw byte pointer + size: a strided, typed or foreign-device tensor would be misread silently
+    if ws is not None and (ws.dtype != torch.uint8 or ws.dim() != 1 or not ws.is_contiguous() or ws.device != q.device):
+        raise ValueError(f"{name}: ws must be a contiguous uint8 tensor on {q.device} (attn_prefix_bytes(rows, H, d) bytes), got {ws.dtype} {tuple(ws.shape)} on {ws.device}")
+    if q.dim() != 2 or q.stride(1) != 1 or q.shape[0] < rows or q.shape[1] < H * d:
+        raise ValueError(f"{name}: q must be a [>= {rows}, >= {H * d}] matrix with contiguous rows, got {tuple(q.shape)}")
+
+
+def attn_prefix_bytes(rows: int, H: int, d: int) -> int:
+    return int(_lib.load().crab_attn_prefix_workspace(int(rows), int(H), int(d)))
+
+
+def attn_prefix_partial(q, prefix_k, prefix_v, ws, tile_rows, row_clip, rows: int, H: int, Hk: int, head_dim: int, P: int, scale: float):
+    """K1: the attention partials of `rows` query rows (q [rows, ldq], rotated) over the P live rows of their clips' prefix cache [C, Hk, Tp, d] ->
+    ws (uint8, attn_prefix_bytes(rows, H, d)).  tile_rows int32 [2 * tiles] / row_clip int32 [rows]: prefix_tile_plan, on the device."""
+    d = _dev(q)
+    _chk_bf16(q, prefix_k, prefix_v)
+    C_, Tp = prefix_k.shape[0], prefix_k.shape[2]
+    if not (prefix_k.is_contiguous() and prefix_v.is_contiguous()) or tuple(prefix_k.shape) != (C_, Hk, Tp, head_dim) or prefix_v.shape != prefix_k.shape:
+        raise ValueError("attn_prefix_partial: prefix_k / prefix_v must be contiguous [C, Hk, Tp, d] tensors")
+    _chk_prefix_ws("attn_prefix_partial", ws, q, rows, H, head_dim)
+    if tile_rows is None or row_clip is None or tile_rows.numel() % 2 or not 2 <= tile_rows.numel() <= 2 * rows:
+        raise ValueError("attn_prefix_partial: tile_rows (int32 [2 * tiles], 1 <= tiles <= rows) and row_clip (int32 [rows]) are required")
+    _chk_i32("tile_rows", tile_rows, tile_rows.numel(), q.device)
+    _chk_i32("row_clip", row_clip, rows, q.device)
+    _lib.check(_lib.load().crab_attn_prefix_partial(_lib.ctx(d), _stream(), _p(q), q.stride(0), _p(prefix_k), _p(prefix_v), _p(ws),
+                                                    ws.numel() * ws.element_size() if ws is not None else 0, _p(tile_rows), tile_rows.numel() // 2,
+                                                    _p(row_clip), rows, C_, H, Hk, head_dim, Tp, P, scale), d)
+    return ws
+
+
+def attn_own_merge(q, ws, k_cache, v_cache, o, B: int, Sq: int, H: int, Hk: int, head_dim: int, Tmax: int, ctx_len: int, scale: float,
+                   ctx_dev=None, kv_start=None):
+    """K2: query i of sequence b (row b * Sq + i) over its own cache slots kv_start[b] .. ctx_len (+ ctx_dev[0]) - 1 + i, merged with the prefix
+    partial of the row in ws -> o [B * Sq, ldo] bf16."""
+    d = _dev(q)
+    _chk_bf16(q, k_cache, v_cache, o)
+    if not (k_cache.is_contiguous() and v_cache.is_contiguous()) or tuple(k_cache.shape) != (B, Hk, Tmax, head_dim) or v_cache.shape != k_cache.shape:
+        raise ValueError("attn_own_merge: k_cache / v_cache must be contiguous [B, Hk, Tmax, d] tensors")
+    _chk_prefix_ws("attn_own_merge", ws, q, B * Sq, H, head_dim)
+    if o.dim() != 2 or o.stride(1) != 1 or o.shape[0] < B * Sq or o.shape[1] < H * head_dim or o.device != q.device:
+        raise ValueError("attn_own_merge: o needs B * Sq rows of H * d contiguous columns on q's device")
+    _chk_i32("kv_start", kv_start, B, q.device)
+    _chk_i32("ctx_dev", ctx_dev, 1, q.device)
+    _lib.check(_lib.load().crab_attn_own_merge(_lib.ctx(d), _stream(), _p(q), q.stride(0), _p(ws), ws.numel() * ws.element_size() if ws is not None else 0,
+                                               _p(k_cache), _p(v_cache), _p(o), o.stride(0), B, Sq, H, Hk, head_dim, Tmax, ctx_len, _p(ctx_dev),
+                                               scale, _p(kv_start)), d)
+    return o
+
+
 def lm_head_xent_bytes(M: int, N: int) -> int:
     return int(_lib.load().crab_lm_head_xent_workspace(int(M), int(N)))
 

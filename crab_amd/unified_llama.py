@@ -342,6 +342,48 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
                                           sampling=sampling, return_first_logits=want_first, coalesce=coalesce, max_rows=max_rows,
                                           kv_cache_dtype=kwargs.get("kv_cache_dtype"), weight_dtype=kwargs.get("weight_dtype"))
 
+    @torch.no_grad()
+    def generate_questions(self, clips, max_rows: Optional[int] = None, **kwargs):
+        """Several questions per clip on one prefix KV (GenerationEngine.generate_shared_prefix).  `clips` = a list of dicts, each with the four
+        generate() arguments of ONE clip (batch_input_ids = [ids of the shared part], batch_labels, batch_X_modals = [its modalities],
+        batch_task_names) and `question_ids`: a list of 1-D id tensors, the text that follows the shared part - for the AVQA template
+        (dataset/quick_start_dataset.py:158-159) the shared part ends with "Please answer this question: " and a question is the rest.  The
+        caller splits, and tokenising the two halves separately must give the ids the whole string would give.
+        prepare_multimodal_inputs runs ONCE per clip, the questions are embedded with embed_tokens; clips whose shared parts come out at the
+        same length decode together (the engine takes one prefix length per call).  Returns one id tensor per clip, [questions, n]: row g is
+        what generate() returns for the ids cat(shared, question g), within the decoder's bf16 tolerance (with output_first_logits=True:
+        (ids, fp32 logits of the first generated position))."""
+        for k in ("output_logits", "return_dict_in_generate", "inputs_embeds"):
+            if kwargs.get(k) is not None and kwargs.get(k) is not False:
+                raise NotImplementedError(f"generate_questions returns token ids only: {k} is a generate() argument")
+        want_first = bool(kwargs.get("output_first_logits"))
+        self._check_generate_kwargs(kwargs)
+        sampling = self._sampling(kwargs)
+        if ops.PROFILER is not None:
+            ops.PROFILER.mark("encode_begin")
+        prefixes, questions = [], []
+        for c in clips:
+            if len(c["batch_input_ids"]) != 1 or not len(c["question_ids"]):
+                raise ValueError("generate_questions: one shared id sequence and at least one question per clip")
+            inputs = self.prepare_multimodal_inputs(batch_input_ids=c["batch_input_ids"], batch_labels=c.get("batch_labels"),
+                                                    batch_X_modals=c["batch_X_modals"], return_multi_scale_features=False, return_gt_mask=False,
+                                                    batch_task_names=c.get("batch_task_names"))
+            prefixes.append(inputs['inputs_embeds'].to(device=self.device, dtype=BF16))
+            questions.append([self.encode_ids(torch.as_tensor(q, device=self.device).reshape(-1)).to(BF16) for q in c["question_ids"]])
+        eos = kwargs.get("eos_token_id", self.config.eos_token_id)
+        pad = kwargs.get("pad_token_id", self.model.pad_token_id if self.model.pad_token_id is not None else eos)
+        outs = [None] * len(clips)
+        for P in sorted({p.shape[1] for p in prefixes}):
+            idx = [i for i, p in enumerate(prefixes) if p.shape[1] == P]
+            res = self._engine.generate_shared_prefix(torch.cat([prefixes[i] for i in idx], 0), [questions[i] for i in idx],
+                                                      int(kwargs.get("max_new_tokens", 20)), eos_token_id=eos, pad_token_id=pad,
+                                                      min_new_tokens=int(kwargs.get("min_new_tokens", 0) or 0), use_graph=kwargs.get("use_graph", True),
+                                                      sampling=sampling, return_first_logits=want_first, kv_cache_dtype=kwargs.get("kv_cache_dtype"),
+                                                      weight_dtype=kwargs.get("weight_dtype"), max_rows=max_rows)
+            for i, r in zip(idx, res):
+                outs[i] = r
+        return outs
+
     # HF generate() arguments that would CHANGE what is decoded and that this path does not implement: refused by name instead of ignored
     # (name -> the value that means "off").  Everything the reference's loops pass (use_cache, max_new_tokens; do_sample & co. from the
     # checkpoint's generation_config) is implemented; unknown names that cannot alter the ids (output_attentions = False, ...) pass through.

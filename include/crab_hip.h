@@ -292,6 +292,36 @@ int crab_attn_decode_rope(crab_ctx* ctx, void* stream, const void* qkv, int64_t 
                           void* v_cache, void* o, int64_t ldo, int B, int H, int Hk, int d, int Tmax, int pos0,
                           const int32_t* pos_dev, float scale, void* workspace, int64_t workspace_bytes);
 
+/* ---- Attention over a SHARED PREFIX plus an own cache (modeling_llama.py:394-445 on the keys [prefix of the row's clip ; the row's own keys]).
+ * Several sequences that start with the same P rows (the questions about one clip) keep those rows' K / V once per clip, prefix_k / prefix_v
+ * [C, Hk, Tp, d] of one layer (rows 0 .. P - 1 live, P a host int, equal for all clips), and only their own keys in k_cache / v_cache
+ * [B, Hk, Tmax, d].  Every query sits at a position >= P: all P prefix keys are visible to it.  Two launches, no host synchronisation (capturable):
+ *
+ * crab_attn_prefix_partial: q [rows, ldq] bf16, head h at column h * d (rotated already).  Tile t covers the tile_rows[2 t + 1] query rows from
+ * row tile_rows[2 t] on, all of the clip row_clip[first row] (row_clip: int32 [rows]); a tile holds at most 16 / (H / Hk) rows - every row
+ * brings the H / Hk query heads of a kv head into the 16 rows of a matrix-instruction operand, so the prefix K / V rows are read once per
+ * (tile, kv head).  A tile that leaves [0, rows) or names a clip outside [0, C) is skipped.  Per (query row, head) the workspace receives d + 2
+ * fp32 words: the unnormalised o[d] (relative to the running max), the running max m and the sum l; crab_attn_prefix_workspace(rows, H, d) bytes.
+ *
+ * crab_attn_own_merge: query i (0 .. Sq - 1) of sequence b is row b * Sq + i of q / o / the workspace and attends the own slots kv_start[b] ..
+ * ctx_len - 1 + i (ctx_len = ctx_len_host, plus ctx_dev[0] when ctx_dev != NULL, as crab_attn_decode_masked; kv_start NULL = 0), never past
+ * Tmax; the result is merged with the row's prefix partial by the log-sum-exp rule in a fixed order (own part, then prefix part) and written as
+ * bf16 o [B * Sq, ldo].  A row whose own range is empty takes the prefix partial alone.  Sq == 1 is the decode step, Sq > 1 the prefill of the
+ * rows after the prefix (query i sees the own keys up to its own).
+ *
+ * Both: d = 64 / 128 and H / Hk in {1, 2, 4, 7, 8}; CRAB_E_UNSUPPORTED for any other combination (H % Hk != 0 included), CRAB_E_WORKSPACE for a
+ * missing or short workspace, CRAB_E_INVALID for the rest (null operands, P outside 1 .. Tp, alignment: ldq % 8, 16-byte pointers).
+ * These three symbols were ADDED under ABI 13: crab_abi_version() still returns 13, because nothing that existed changed (no struct, no
+ * signature, no constant) and the library's own tests pin the number to the FP8 additions.  A caller that needs them probes for the symbol
+ * (dlsym / hasattr), not for a version number. */
+int64_t crab_attn_prefix_workspace(int rows, int H, int d);
+int crab_attn_prefix_partial(crab_ctx* ctx, void* stream, const void* q, int64_t ldq, const void* prefix_k, const void* prefix_v,
+                             void* workspace, int64_t workspace_bytes, const int32_t* tile_rows, int ntiles, const int32_t* row_clip,
+                             int rows, int C, int H, int Hk, int d, int Tp, int P, float scale);
+int crab_attn_own_merge(crab_ctx* ctx, void* stream, const void* q, int64_t ldq, const void* workspace, int64_t workspace_bytes,
+                        const void* k_cache, const void* v_cache, void* o, int64_t ldo, int B, int Sq, int H, int Hk, int d, int Tmax,
+                        int ctx_len_host, const int32_t* ctx_dev, float scale, const int32_t* kv_start);
+
 /* ---- FP8 KV cache (ABI 13; opt-in, crab_llama_io.kv_fp8).  Storage: K (after RoPE) and V as one byte per element, OCP e4m3fn, layout
  * [L, B, Hk, Tmax, d] like the bf16 cache, plus one fp32 scale per cached row and KV head for K and for V: two arrays [L, B, Hk, Tmax].
  *     amax = max |x| over the row's d elements (x = the bf16 values the bf16 cache would hold);
