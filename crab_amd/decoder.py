@@ -219,6 +219,7 @@ class GenerationEngine:
         self._kv = {}
         self._dec = {}                 # slot -> persistent decode state (+ captured graph)
         self._prefix = None            # generate_shared_prefix: the persistent buffers of the last wave shape (_shared_prefix_buffers: two _SharedPrefix forms)
+        self._tries = {}               # TokenTrie.key -> device copies of its CSR arrays (constrained generation; dropped by invalidate())
         self._attn_ws = {}             # B -> scratch of the fused small-batch attention for calls that run in the SHARED prefill workspace (_attn_scratch)
         self.kv_budget_bytes = None    # None: ask the device (hipMemGetInfo); an int caps what generate() may plan with (tests)
         self.last_plan = None          # what the last generate() decided: {"B", "groups", "bytes_per_seq", "budget"}
@@ -321,6 +322,7 @@ class GenerationEngine:
         self._ws = {}
         self._kv = {}
         self._attn_ws = {}
+        self._tries = {}
         self._prefix = None
         self._table = None
         self._table8 = None
@@ -976,6 +978,37 @@ class GenerationEngine:
         return ScoreOutput(mean.reshape(()), s, nt, nc, toks)
 
     # ------------------------------------------------------------------ decode
+    def _constraints(self, constraint, counts: List[int], eos_token_id, min_new_tokens: int, flat: bool = False):
+        """The `constraint` argument of generate() / generate_many() / generate_shared_prefix - (TokenTrie, set indices) or None - as one
+        _Constraint per group of `counts` rows.  The set indices come as the rows come: one list per group, or (flat) one list for the one group
+        (None: set 0 everywhere, an error when the trie holds several sets).  eos_token_id / min_new_tokens are checked against the trie (ValueError by
+        name).  The device copies of the CSR arrays are made once per trie CONTENT and kept until invalidate(), so repeated calls with the same
+        sets meet the same pointers and reuse the captured graph."""
+        if constraint is None:
+            return [None] * len(counts)
+        from .constrain import TokenTrie, rows_of
+        trie, sets = constraint if isinstance(constraint, (tuple, list)) else (constraint, None)
+        if not isinstance(trie, TokenTrie):
+            raise ValueError("constraint must be (TokenTrie, set indices) - crab_amd.constrain.as_trie builds one from id sequences")
+        trie.check(eos_token_id, min_new_tokens, self.lm_head.weight.shape[0])
+        if sets is not None and flat:
+            sets = [sets]
+        if sets is not None and len(sets) != len(counts):
+            raise ValueError(f"allowed_set: {len(sets)} lists of set indices for {len(counts)} groups of rows")
+        cache = self.__dict__.setdefault("_tries", {})
+        dev = cache.get(trie.key)
+        if dev is None or dev.edge_off.device != self.device:
+            up = lambda a: torch.from_numpy(a.copy()).to(self.device)
+            dev = types.SimpleNamespace(edge_off=up(trie.edge_off), edge_tok=up(trie.edge_tok), edge_dst=up(trie.edge_dst), n_nodes=trie.n_nodes,
+                                        n_edges=trie.n_edges)
+            dev.key = ("trie", dev.edge_off.data_ptr(), dev.edge_tok.data_ptr(), dev.edge_dst.data_ptr(), dev.n_nodes, dev.n_edges)
+            cache[trie.key] = dev
+        out = []
+        for g, n in enumerate(counts):
+            idx = rows_of(trie, None if sets is None else sets[g], n)
+            out.append(_Constraint(dev, [int(trie.roots[i]) for i in idx]))
+        return out
+
     def _decode_step(self, st: "_DecodeState"):
         """One greedy step entirely on device: embed(cur_ids) -> layers -> norm -> lm_head -> greedy select -> advance."""
         c = self.cfg
@@ -992,20 +1025,27 @@ class GenerationEngine:
 
     def _select(self, st: "_DecodeState"):
         """Next token of every row from st.logits: greedy (argmax) or, with st.sampling = (temperature, top_k, top_p, seed), HF's sample
-        mode (temperature -> top-k -> top-p -> draw) - both device-resident, so the step stays capturable."""
-        if st.sampling is None:
+        mode (temperature -> top-k -> top-p -> draw) - both device-resident, so the step stays capturable.  A state with a token trie (st.trie:
+        closed-set generation) takes both among the out-edges of every row's node instead (ops.constrained_select; st.node follows the edge)."""
+        if st.trie is not None:
+            t, k, p_, seed = st.sampling if st.sampling is not None else (0.0, 0, 1.0, 0)
+            ops.constrained_select(st.logits, st.trie.edge_off, st.trie.edge_tok, st.trie.edge_dst, st.node, st.cur_ids, st.out_ids, st.step_dev,
+                                   st.finished, st.eos, st.pad, st.min_new, t, k, p_, seed + 7919 * st.slot)
+        elif st.sampling is None:
             ops.greedy_select(st.logits, st.cur_ids, st.out_ids, st.step_dev, st.finished, st.eos, st.pad, st.min_new)
         else:
             t, k, p_, seed = st.sampling
             ops.sample_select(st.logits, st.cur_ids, st.out_ids, st.step_dev, st.finished, st.eos, st.pad, st.min_new, t, k, p_, seed + 7919 * st.slot)
 
     def _state(self, B: int, S: int, max_new_tokens: int, eos_token_id, pad_token_id, min_new_tokens: int, return_hidden: bool, slot: int,
-               sampling=None, ragged: bool = False, extra_key=()) -> "_DecodeState":
+               sampling=None, ragged: bool = False, extra_key=(), constraint=None) -> "_DecodeState":
         """The persistent decode state of `slot` for B sequences whose (longest) prompt has S rows: KV cache, per-row words, logits and the HIP
         graph captured over them.  Kept per slot and reused by every call whose shapes, flags and buffers are the same: the key holds
         everything the captured launches bake in (pointers included).  ragged: the state of a coalesced batch (generate_many(coalesce=True)) -
         it owns a row_off word per row (first cache slot of the row's sequence) that the captured decode step reads.  extra_key: what else a caller's captured step bakes in
-        (generate_shared_prefix: the prefix cache, its length, the tile plan and the workspace)."""
+        (generate_shared_prefix: the prefix cache, its length, the tile plan and the workspace).  constraint: the rows' _Constraint (closed-set
+        generation) - the trie's device pointers enter the key, so a captured graph never crosses tries, and every call puts the rows back on
+        their roots."""
         if int(max_new_tokens) < 1:                             # HF: GenerationConfig.validate() - "`max_new_tokens` must be greater than 0"; here the first token's slot would not exist
             raise ValueError(f"`max_new_tokens` must be greater than 0, but is {max_new_tokens}.")
         dev = self.device
@@ -1032,7 +1072,8 @@ class GenerationEngine:
                tab.data_ptr(), self.lm_head.weight.data_ptr(), self.model.embed_tokens.weight.data_ptr(),
                self.model.layers[0].self_attn._qkv.W.data_ptr(),
                self.model.layers[0].self_attn._qkv.RA is not None, sampling, bool(ragged),
-               self._kv_mode, ks.data_ptr() if ks is not None else 0, vs.data_ptr() if vs is not None else 0, w8_key) + tuple(extra_key)
+               self._kv_mode, ks.data_ptr() if ks is not None else 0, vs.data_ptr() if vs is not None else 0, w8_key) + tuple(extra_key) + \
+            (constraint.dev.key if constraint is not None else ())
         st = self._dec.get(slot)
         if st is None or st.key != key:
             st = _DecodeState()
@@ -1051,10 +1092,15 @@ class GenerationEngine:
             st.eos, st.pad, st.min_new, st.want_hidden = eos, pad, int(min_new_tokens), bool(return_hidden)
             st.sampling = sampling
             st.prefix = None
+            st.trie = constraint.dev if constraint is not None else None
+            st.node = torch.empty((B,), device=dev, dtype=torch.int32) if constraint is not None else None
             self._dec[slot] = st
         st.S = S
         st.cur_ids.zero_(); st.out_ids.fill_(pad_token_id if pad_token_id is not None else 0); st.finished.zero_()
         st.pos_dev.fill_(S - 1); st.step_dev.zero_()
+        if constraint is not None:
+            assert len(constraint.roots) == B, "one trie root per row"
+            st.node.copy_(torch.tensor(constraint.roots, dtype=torch.int32))
         return st
 
     def _prefill_chunk(self, st: "_DecodeState", emb: torch.Tensor, b0: int, t0: int = 0, pos_ids=None, kv_start=None):
@@ -1072,10 +1118,10 @@ class GenerationEngine:
         ops.kv_quant_fp8(sk, sv, st.kc, st.vc, st.ks, st.vs, b0=b0, t0=0, t_dst=t0, S=S, row_off=kv_start)
 
     def _start(self, embeds: torch.Tensor, max_new_tokens: int, eos_token_id, pad_token_id, min_new_tokens: int, prefill_chunk: int,
-               return_hidden: bool, slot: int, sink=None, sampling=None) -> "_DecodeState":
+               return_hidden: bool, slot: int, sink=None, sampling=None, constraint=None) -> "_DecodeState":
         """Allocate the decode state of one group of sequences, prefill it and select its first token."""
         B, S, D = embeds.shape
-        st = self._state(B, S, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, return_hidden, slot, sampling)
+        st = self._state(B, S, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, return_hidden, slot, sampling, constraint=constraint)
         # ---- prefill in chunks of sequences (bounds activation memory, keeps GEMM M in the MFMA-efficient range)
         chunks = self.plan_prefill_chunks(B, S) if not prefill_chunk else [prefill_chunk] * (B // prefill_chunk) + \
             ([B % prefill_chunk] if B % prefill_chunk else [])
@@ -1121,7 +1167,7 @@ class GenerationEngine:
             g = g1 + 1
 
     def _start_ragged(self, embeds_list: List[torch.Tensor], max_new_tokens: int, eos_token_id, pad_token_id, min_new_tokens: int,
-                      sink=None, sampling=None, return_hidden: bool = False) -> "_DecodeState":
+                      sink=None, sampling=None, return_hidden: bool = False, constraint=None) -> "_DecodeState":
         """The decode state of SEVERAL generate() calls coalesced into one batch.  Group g = [B_g, S_g, D] is one call of the eval loop: its
         own prompt length and left padding, positions 0 .. S_g - 1 (unified_llama.py:262-267).  All rows share one KV cache [L, sum B_g, Hk,
         Tmax, d] in which every group is RIGHT-ALIGNED at Smax = max S_g: group g's prompt occupies slots Smax - S_g .. Smax - 1, so the token
@@ -1133,7 +1179,8 @@ class GenerationEngine:
         Bs = [int(e.shape[0]) for e in embeds_list]
         Ss = [int(e.shape[1]) for e in embeds_list]
         Bt, Smax = sum(Bs), max(Ss)
-        st = self._state(Bt, Smax, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, return_hidden, 0, sampling, ragged=True)
+        st = self._state(Bt, Smax, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, return_hidden, 0, sampling, ragged=True,
+                         constraint=constraint)
         st.row_off.copy_(torch.tensor([Smax - S for B, S in zip(Bs, Ss) for _ in range(B)], dtype=torch.int32), non_blocking=False)
         waste = sum(B * (Smax - S) for B, S in zip(Bs, Ss)) / max(1, sum(B * S for B, S in zip(Bs, Ss)))
         if len(set(Ss)) > 1 and waste <= RAGGED_PAD_MAX:
@@ -1183,10 +1230,16 @@ class GenerationEngine:
     def generate(self, embeds: torch.Tensor, max_new_tokens: int, eos_token_id: Optional[int] = None,
                  pad_token_id: Optional[int] = None, min_new_tokens: int = 0, prefill_chunk: int = 0, use_graph: bool = True,
                  return_step_logits: bool = False, return_hidden: bool = False, decode_streams: int = 1,
-                 return_first_logits: bool = False, sampling=None, kv_cache_dtype: Optional[str] = None, weight_dtype: Optional[str] = None):
-        """kv_cache_dtype / weight_dtype: "bf16" / "fp8_e4m3" for this call (None: the engine's); see _generate for the rest."""
+                 return_first_logits: bool = False, sampling=None, kv_cache_dtype: Optional[str] = None, weight_dtype: Optional[str] = None,
+                 constraint=None):
+        """kv_cache_dtype / weight_dtype: "bf16" / "fp8_e4m3" for this call (None: the engine's); see _generate for the rest.
+        constraint = (TokenTrie, one set index per row or None): closed-set generation (crab_amd/constrain.py) - every row's ids, cut at EOS,
+        are a member of the row's answer set; greedy and sample mode both choose among the trie's edges on the device, everything else (KV and
+        weight modes, EOS trim, padding of finished rows) is unchanged.  A row that max_new_tokens cuts in the middle of an answer holds a
+        proper prefix of a member, as HF's constrained decode does."""
+        cons, = self._constraints(constraint, [int(embeds.shape[0])], eos_token_id, min_new_tokens, flat=True)
         return self._call(kv_cache_dtype, weight_dtype, self._generate, embeds, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens,
-                          prefill_chunk, use_graph, return_step_logits, return_hidden, decode_streams, return_first_logits, sampling)
+                          prefill_chunk, use_graph, return_step_logits, return_hidden, decode_streams, return_first_logits, sampling, cons)
 
     def _run_steps(self, sts: List["_DecodeState"], max_new_tokens: int, graphed: bool, side_streams: bool, retire: bool, on_step=None,
                    sampled_step=None):
@@ -1240,7 +1293,7 @@ class GenerationEngine:
     def _generate(self, embeds: torch.Tensor, max_new_tokens: int, eos_token_id: Optional[int] = None,
                   pad_token_id: Optional[int] = None, min_new_tokens: int = 0, prefill_chunk: int = 0, use_graph: bool = True,
                   return_step_logits: bool = False, return_hidden: bool = False, decode_streams: int = 1,
-                  return_first_logits: bool = False, sampling=None):
+                  return_first_logits: bool = False, sampling=None, constraint=None):
         """Greedy generation from inputs_embeds only, as UnifiedForCausalLM.generate drives HF generate
         (unified_llama.py:262-267): positions 0..S-1 (left pads attended), returns ONLY new ids.
 
@@ -1257,7 +1310,7 @@ class GenerationEngine:
         groups = self.plan_batch(B, S, max_new_tokens, slots=max(1, decode_streams))
         if len(groups) > 1:
             return self._generate_split(groups, embeds, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, prefill_chunk, use_graph,
-                                        return_step_logits, return_hidden, return_first_logits, sampling)
+                                        return_step_logits, return_hidden, return_first_logits, sampling, constraint)
         graphed = use_graph and max_new_tokens > 2
         G = decode_streams if (decode_streams > 1 and graphed and B >= decode_streams and
                                not return_step_logits and not return_hidden) else 1
@@ -1286,7 +1339,8 @@ class GenerationEngine:
         for g in range(G):
             with _ws_slot(g):
                 sts.append(self._start(embeds[B * g // G:B * (g + 1) // G], max_new_tokens, eos_token_id, pad_token_id, min_new_tokens,
-                                       prefill_chunk, return_hidden, g, sink, sampling))
+                                       prefill_chunk, return_hidden, g, sink, sampling,
+                                       constraint.rows(B * g // G, B * (g + 1) // G) if constraint is not None else None))
         if ops.PROFILER is not None:
             ops.PROFILER.mark("prefill_end")
         # the groups are ONE call: all of them step until all have finished (a retired group's buffer would hold the fill value, not its pad id)
@@ -1311,15 +1365,18 @@ class GenerationEngine:
                       pad_token_id: Optional[int] = None, min_new_tokens: int = 0, use_graph: bool = True, sampling=None,
                       return_first_logits: bool = False, coalesce: bool = False, max_rows: Optional[int] = None,
                       return_step_logits: bool = False, return_hidden: bool = False, kv_cache_dtype: Optional[str] = None,
-                      weight_dtype: Optional[str] = None):
-        """kv_cache_dtype / weight_dtype: "bf16" / "fp8_e4m3" for this call (None: the engine's); see _generate_many for the rest."""
+                      weight_dtype: Optional[str] = None, constraint=None):
+        """kv_cache_dtype / weight_dtype: "bf16" / "fp8_e4m3" for this call (None: the engine's); see _generate_many for the rest.
+        constraint = (TokenTrie, one list of set indices per batch or None): closed-set generation as in generate(); the set indices follow
+        their rows into the in-flight states and the ragged waves."""
+        cons = self._constraints(constraint, [int(e.shape[0]) for e in embeds_list], eos_token_id, min_new_tokens) if constraint is not None else None
         return self._call(kv_cache_dtype, weight_dtype, self._generate_many, embeds_list, max_new_tokens, eos_token_id, pad_token_id,
-                          min_new_tokens, use_graph, sampling, return_first_logits, coalesce, max_rows, return_step_logits, return_hidden)
+                          min_new_tokens, use_graph, sampling, return_first_logits, coalesce, max_rows, return_step_logits, return_hidden, cons)
 
     def _generate_many(self, embeds_list: List[torch.Tensor], max_new_tokens: int, eos_token_id: Optional[int] = None,
                        pad_token_id: Optional[int] = None, min_new_tokens: int = 0, use_graph: bool = True, sampling=None,
                        return_first_logits: bool = False, coalesce: bool = False, max_rows: Optional[int] = None,
-                       return_step_logits: bool = False, return_hidden: bool = False):
+                       return_step_logits: bool = False, return_hidden: bool = False, constraints=None):
         """Several INDEPENDENT batches in flight: each element of `embeds_list` ([B_i, S_i, D], its own prompt length and left padding, i.e.
         exactly what one generate() call of the reference's eval loop gets) becomes one decode group with its own KV cache, decode state
         and captured HIP graph; the groups are prefilled one after the other and their decode steps are replayed on separate HIP streams.
@@ -1343,14 +1400,15 @@ class GenerationEngine:
         if not embeds_list:
             return []
         G = len(embeds_list)
+        cons = constraints if constraints is not None else [None] * G      # one _Constraint per batch
         if (return_step_logits or return_hidden) and (not coalesce or return_first_logits or (return_step_logits and return_hidden)):
             raise NotImplementedError("generate_many: return_step_logits / return_hidden are options of the coalesced form, one at a time (use generate() per batch otherwise)")
         if coalesce and (G > 1 or return_step_logits or return_hidden):
             return self._generate_coalesced(embeds_list, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling,
-                                            return_first_logits, max_rows, return_step_logits, return_hidden)
+                                            return_first_logits, max_rows, return_step_logits, return_hidden, cons)
         if G == 1:
             return [self._generate(embeds_list[0], max_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id, min_new_tokens=min_new_tokens,
-                                   use_graph=use_graph, sampling=sampling, return_first_logits=return_first_logits)]
+                                   use_graph=use_graph, sampling=sampling, return_first_logits=return_first_logits, constraint=cons[0])]
         need = sum(e.shape[0] * self.bytes_per_sequence(e.shape[1], max_new_tokens) for e in embeds_list) + self.fixed_bytes(max(e.shape[0] for e in embeds_list),
                                                                                                                             max(e.shape[1] for e in embeds_list))
         budget = self.memory_budget(0, 0, slots=G)
@@ -1366,7 +1424,7 @@ class GenerationEngine:
         sts = []
         for g, emb in enumerate(embeds_list):
             with _ws_slot(g):
-                sts.append(self._start(emb, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, 0, False, g, sink, sampling))
+                sts.append(self._start(emb, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, 0, False, g, sink, sampling, cons[g]))
         self._run_steps(sts, max_new_tokens, use_graph and max_new_tokens > 2, True, True)
         outs = []
         for g, st in enumerate(sts):
@@ -1375,7 +1433,7 @@ class GenerationEngine:
         return outs
 
     def _generate_coalesced(self, embeds_list, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling,
-                            return_first_logits, max_rows, return_step_logits=False, return_hidden=False):
+                            return_first_logits, max_rows, return_step_logits=False, return_hidden=False, cons=None):
         """generate_many(coalesce=True): pack the batches, in order, into waves of at most `cap` rows (the weight-streaming regime of the decode
         projections, and what the device's memory holds at the longest prompt), run every wave as one ragged batch."""
         Bs = [int(e.shape[0]) for e in embeds_list]
@@ -1387,22 +1445,25 @@ class GenerationEngine:
         waves = _pack_waves(Bs, max(1, min(cap, fit)))
         plan = {"B": sum(Bs), "groups": [sum(Bs[g] for g in w) for w in waves], "bytes_per_seq": per, "budget": budget, "coalesced": True}
         outs = [None] * len(embeds_list)
+        cons = cons if cons is not None else [None] * len(embeds_list)
         for w in waves:
             if len(w) == 1:                                    # a lone batch (or one larger than the cap: _generate plans its own split)
                 g = w[0]
                 outs[g] = self._generate(embeds_list[g], max_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
                                          min_new_tokens=min_new_tokens, use_graph=use_graph, sampling=sampling, return_first_logits=return_first_logits,
-                                         return_step_logits=return_step_logits, return_hidden=return_hidden)
+                                         return_step_logits=return_step_logits, return_hidden=return_hidden, constraint=cons[g])
                 continue
+            # the rows of the wave are the rows of its batches in wave order: so are their trie roots
+            wc = _Constraint(cons[w[0]].dev, [r for g in w for r in cons[g].roots]) if cons[w[0]] is not None else None
             res = self._ragged_wave([embeds_list[g] for g in w], max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling,
-                                    return_first_logits, return_step_logits, return_hidden)
+                                    return_first_logits, return_step_logits, return_hidden, wc)
             for g, r in zip(w, res):
                 outs[g] = r
         self.last_plan = plan
         return outs
 
     def _ragged_wave(self, embeds_list, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling, return_first_logits,
-                     return_step_logits=False, return_hidden=False):
+                     return_step_logits=False, return_hidden=False, constraint=None):
         firsts, steps = [], []
 
         def sink(st):
@@ -1414,7 +1475,7 @@ class GenerationEngine:
                 steps.append(st.hn.clone())
 
         with _ws_slot(0):
-            st = self._start_ragged(embeds_list, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, sink, sampling, return_hidden)
+            st = self._start_ragged(embeds_list, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, sink, sampling, return_hidden, constraint)
         if ops.PROFILER is not None:
             ops.PROFILER.mark("prefill_end")
         self._run_steps([st], max_new_tokens, use_graph and max_new_tokens > 2, False, True,
@@ -1500,7 +1561,7 @@ class GenerationEngine:
     def generate_shared_prefix(self, prefix_embeds: torch.Tensor, suffix_embeds, max_new_tokens: int, eos_token_id: Optional[int] = None,
                                pad_token_id: Optional[int] = None, min_new_tokens: int = 0, use_graph: bool = True, sampling=None,
                                return_first_logits: bool = False, return_step_logits: bool = False, kv_cache_dtype: Optional[str] = None,
-                               weight_dtype: Optional[str] = None, max_rows: Optional[int] = None):
+                               weight_dtype: Optional[str] = None, max_rows: Optional[int] = None, constraint=None):
         """Several questions per clip on ONE prefix KV.  prefix_embeds [C, P, D] bf16: the shared part of C clips (everything up to the question
         text; the same P for all).  suffix_embeds: C lists, one [S_cg, D] tensor per question of the clip.  Returns one id tensor per clip,
         [G_c, n] (with return_first_logits (ids, fp32 [G_c, V]); with return_step_logits (ids, fp32 [G_c, n, V])): what
@@ -1516,12 +1577,14 @@ class GenerationEngine:
         tile, so clips with different numbers of questions mix freely and no tile spans two clips (ops.prefix_tile_plan).
         More rows than a decode step takes (ops.DECODE_MAX_ROWS, max_rows) or than fit the memory run as consecutive waves of whole clips
         (plan_shared_prefix).  Sample mode draws per (seed, step, row of the wave), as the coalesced form does.
-        kv_cache_dtype = "fp8_e4m3" and weight_dtype = "fp8_e4m3" raise NotImplementedError: the shared prefix is a bf16 path."""
+        kv_cache_dtype = "fp8_e4m3" and weight_dtype = "fp8_e4m3" raise NotImplementedError: the shared prefix is a bf16 path.
+        constraint = (TokenTrie, one list per clip with one set index per question, or None): closed-set generation as in generate()."""
+        cons = self._constraints(constraint, [len(qs) for qs in suffix_embeds], eos_token_id, min_new_tokens) if constraint is not None else None
         return self._call(kv_cache_dtype, weight_dtype, self._generate_shared_prefix, prefix_embeds, suffix_embeds, max_new_tokens, eos_token_id,
-                          pad_token_id, min_new_tokens, use_graph, sampling, return_first_logits, return_step_logits, max_rows)
+                          pad_token_id, min_new_tokens, use_graph, sampling, return_first_logits, return_step_logits, max_rows, cons)
 
     def _generate_shared_prefix(self, prefix_embeds, suffix_embeds, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling,
-                                return_first_logits, return_step_logits, max_rows):
+                                return_first_logits, return_step_logits, max_rows, cons=None):
         if self._fp8:
             raise NotImplementedError('kv_cache_dtype="fp8_e4m3" with a shared prefix (generate_shared_prefix) is not implemented: the prefix cache and its attention kernels are bf16')
         if getattr(self, "_w_mode", "bf16") == "fp8_e4m3":
@@ -1538,12 +1601,13 @@ class GenerationEngine:
         Smax = max(int(q.shape[0]) for qs in suffix_embeds for q in qs)
         outs = []
         for w in self.plan_shared_prefix(Gs, P, Smax, max_new_tokens, max_rows):
+            wc = _Constraint(cons[w[0]].dev, [r for c in w for r in cons[c].roots]) if cons is not None else None      # one root per question, in row order
             outs += self._shared_prefix_wave(prefix_embeds[w[0]:w[-1] + 1], [suffix_embeds[c] for c in w], max_new_tokens, eos_token_id, pad_token_id,
-                                             min_new_tokens, use_graph, sampling, return_first_logits, return_step_logits)
+                                             min_new_tokens, use_graph, sampling, return_first_logits, return_step_logits, wc)
         return outs
 
     def _shared_prefix_wave(self, prefix_embeds, suffix_embeds, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling,
-                            return_first_logits, return_step_logits):
+                            return_first_logits, return_step_logits, constraint=None):
         C, P, D = prefix_embeds.shape
         Gs = [len(qs) for qs in suffix_embeds]
         flat = [q for qs in suffix_embeds for q in qs]
@@ -1567,7 +1631,8 @@ class GenerationEngine:
             for n in self.plan_prefill_chunks(C, P):
                 self.prefill(prefix_embeds[b0:b0 + n], px.decode.pk, px.decode.pv, b0=b0, want_logits=False)
                 b0 += n
-            st = self._state(B, Smax, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, False, 0, sampling, ragged=True, extra_key=px.key)
+            st = self._state(B, Smax, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, False, 0, sampling, ragged=True, extra_key=px.key,
+                             constraint=constraint)
             st.prefix = px.decode
             st.row_off.copy_(torch.tensor(lay["first_slot"], dtype=torch.int32))
             px.decode.rope_off.copy_(torch.tensor(lay["rope_off"], dtype=torch.int32))
@@ -1602,7 +1667,7 @@ class GenerationEngine:
         return outs
 
     def _generate_split(self, groups, embeds, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, prefill_chunk, use_graph,
-                        return_step_logits, return_hidden, return_first_logits, sampling=None):
+                        return_step_logits, return_hidden, return_first_logits, sampling=None, constraint=None):
         """The batch does not fit the device's memory in one piece: generate the groups one after the other (rows are independent,
         so the results are those of the one-piece run up to the kernel choice a different M implies) and join them.  A group
         that finished early (EOS) is padded to the longest group's length with pad ids, like HF pads finished rows."""
@@ -1619,7 +1684,8 @@ class GenerationEngine:
                 r = self._generate(embeds[b0:b0 + n], max_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
                                    min_new_tokens=min_new_tokens, prefill_chunk=prefill_chunk, use_graph=use_graph,
                                    return_step_logits=return_step_logits, return_hidden=return_hidden, return_first_logits=return_first_logits,
-                                   sampling=None if sampling is None else (sampling[0], sampling[1], sampling[2], sampling[3] + 104729 * b0))
+                                   sampling=None if sampling is None else (sampling[0], sampling[1], sampling[2], sampling[3] + 104729 * b0),
+                                   constraint=constraint.rows(b0, b0 + n) if constraint is not None else None)
             finally:
                 self.kv_budget_bytes = saved
             parts.append(r if isinstance(r, tuple) else (r,))
@@ -1645,7 +1711,8 @@ class GenerationEngine:
         if st.graph is not None:
             return st.graph
         # warm-up run outside capture is not possible without mutating state; instead snapshot and restore
-        snap = (st.cur_ids.clone(), st.out_ids.clone(), st.finished.clone(), st.pos_dev.clone(), st.step_dev.clone())
+        snap = (st.cur_ids.clone(), st.out_ids.clone(), st.finished.clone(), st.pos_dev.clone(), st.step_dev.clone(),
+                st.node.clone() if st.node is not None else None)
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -1656,6 +1723,8 @@ class GenerationEngine:
         # the warm-up wrote K/V at `pos`; restoring the counters makes the first replay overwrite the same slot
         st.cur_ids.copy_(snap[0]); st.out_ids.copy_(snap[1]); st.finished.copy_(snap[2])
         st.pos_dev.copy_(snap[3]); st.step_dev.copy_(snap[4])
+        if st.node is not None:
+            st.node.copy_(snap[5])                     # the warm-up walked the trie one edge ahead of the ids
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             self._decode_step(st)
@@ -1665,6 +1734,17 @@ class GenerationEngine:
 
 class _DecodeState:
     pass
+
+
+class _Constraint:
+    """Closed-set generation for some rows: dev - the device copies of a TokenTrie's CSR arrays (GenerationEngine._constraints), roots - the
+    root node of every row's answer set.  rows(r0, r1) follows the rows wherever a batch is split."""
+
+    def __init__(self, dev, roots):
+        self.dev, self.roots = dev, list(roots)
+
+    def rows(self, r0: int, r1: int) -> "_Constraint":
+        return _Constraint(self.dev, self.roots[r0:r1])
 
 
 class _SharedPrefix:

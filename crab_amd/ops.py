@@ -677,6 +677,24 @@ def sample_select(logits, cur_ids, out_ids, step_dev, finished, eos_id: int, pad
                                               int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF), d)
 
 
+def constrained_select(logits, edge_off, edge_tok, edge_dst, node, cur_ids, out_ids, step_dev, finished, eos_id: int, pad_id: int,
+                       min_new_tokens: int, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0):
+    """crab_constrained_select: the next token of every row among the out-edges of node[b] in a token trie (CSR int32 arrays, crab_amd/constrain.py),
+    greedy (temperature == 0) or HF sample mode over the allowed tokens; node[b] follows the chosen edge.  Device-resident like greedy_select.
+    logits [B, V] fp32 (a row stride of 0 - one row expanded - is fine: the rows are only read)."""
+    d = _dev(logits)
+    B, V = logits.shape
+    n_nodes, n_edges = int(edge_off.shape[0]) - 1, int(edge_tok.shape[0])
+    _chk_i32("edge_off", edge_off, n_nodes + 1, logits.device)
+    _chk_i32("edge_tok", edge_tok, n_edges, logits.device)
+    _chk_i32("edge_dst", edge_dst, n_edges, logits.device)
+    _chk_i32("node", node, B, logits.device)
+    _lib.check(_lib.load().crab_constrained_select(_lib.ctx(d), _stream(), _p(logits), logits.stride(0), B, V, _p(edge_off), _p(edge_tok), _p(edge_dst),
+                                                   n_nodes, n_edges, _p(node), _p(cur_ids), _p(out_ids), out_ids.stride(0), _p(step_dev), _p(finished),
+                                                   eos_id, pad_id, min_new_tokens, float(temperature), int(top_k), float(top_p),
+                                                   int(seed) & 0xFFFFFFFFFFFFFFFF), d)
+
+
 def advance(pos_dev, step_dev):
     d = _dev(pos_dev)
     _lib.check(_lib.load().crab_advance(_lib.ctx(d), _stream(), _p(pos_dev), _p(step_dev)), d)

@@ -272,9 +272,15 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
         weight_dtype ("bf16" | "fp8_e4m3": the decoder weights the decode steps of this call stream, default the engine's; FP8 serves decode
         batches of at most 16 rows - prefill, larger batches, lm_head, forward() and score() stay on the bf16 weights),
         output_first_logits (ids + the fp32 logits of the first generated position, [B, V]: the record the multi-GPU eval gathers),
-        inputs_embeds (skip prepare_multimodal_inputs)."""
+        inputs_embeds (skip prepare_multimodal_inputs),
+        allowed_sequences / allowed_set (closed-set generation, crab_amd/constrain.py: what replaces prefix_allowed_tokens_fn, which needs a host
+        callback between two tokens and stays refused).  allowed_sequences: a TokenTrie, one list of id sequences (one answer set for every row)
+        or a list of such lists (several sets); allowed_set: one set index per row (default set 0; required with several sets).  Every row's
+        ids, cut at EOS, are then a member of its set - greedy and do_sample alike; needs one eos_token_id, and min_new_tokens at most the
+        shortest member.  A row that max_new_tokens cuts in the middle of an answer holds a proper prefix of a member, as in HF."""
         self._check_generate_kwargs(kwargs)
         sampling = self._sampling(kwargs)
+        constraint = self._constraint(kwargs)
         embeds = kwargs.pop("inputs_embeds", None)
         if ops.PROFILER is not None:
             ops.PROFILER.mark("encode_begin")
@@ -293,7 +299,8 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
                                     min_new_tokens=int(kwargs.get("min_new_tokens", 0) or 0),
                                     prefill_chunk=int(kwargs.get("prefill_chunk", 0)), use_graph=kwargs.get("use_graph", True),
                                     return_step_logits=want_logits, decode_streams=int(kwargs.get("decode_streams", 1)),
-                                    return_first_logits=want_first, sampling=sampling, kv_cache_dtype=kwargs.get("kv_cache_dtype"), weight_dtype=kwargs.get("weight_dtype"))
+                                    return_first_logits=want_first, sampling=sampling, kv_cache_dtype=kwargs.get("kv_cache_dtype"), weight_dtype=kwargs.get("weight_dtype"),
+                                    constraint=constraint)
         if want_logits or want_first:
             res = list(res)
             out = type("GenerateOutput", (), {})()
@@ -316,13 +323,15 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
         coalesce = True: as ONE ragged decode batch (right-aligned in one KV cache, per-row rotary offset and first visible key): the weights
         stream once per step for all batches and the encoders run over the clips of all batches together, so batches of 8 reach the
         throughput of one large generate(); per-batch ids / logits agree with separate calls within the decoder's bf16 tolerance.
-        Returns one id tensor per batch (with output_first_logits=True: (ids, fp32 logits of the first generated position))."""
+        Returns one id tensor per batch (with output_first_logits=True: (ids, fp32 logits of the first generated position)).
+        allowed_sequences / allowed_set: closed-set generation as in generate(); allowed_set is one list of set indices per batch."""
         for k in ("output_logits", "return_dict_in_generate", "inputs_embeds"):
             if kwargs.get(k) is not None and kwargs.get(k) is not False:
                 raise NotImplementedError(f"generate_batches returns token ids only: {k} is a generate() argument")
         want_first = bool(kwargs.get("output_first_logits"))
         self._check_generate_kwargs(kwargs)
         sampling = self._sampling(kwargs)
+        constraint = self._constraint(kwargs)
         if ops.PROFILER is not None:
             ops.PROFILER.mark("encode_begin")
         if coalesce:
@@ -340,7 +349,7 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
         return self._engine.generate_many(embeds, int(kwargs.get("max_new_tokens", 20)), eos_token_id=eos, pad_token_id=pad,
                                           min_new_tokens=int(kwargs.get("min_new_tokens", 0) or 0), use_graph=kwargs.get("use_graph", True),
                                           sampling=sampling, return_first_logits=want_first, coalesce=coalesce, max_rows=max_rows,
-                                          kv_cache_dtype=kwargs.get("kv_cache_dtype"), weight_dtype=kwargs.get("weight_dtype"))
+                                          kv_cache_dtype=kwargs.get("kv_cache_dtype"), weight_dtype=kwargs.get("weight_dtype"), constraint=constraint)
 
     @torch.no_grad()
     def generate_questions(self, clips, max_rows: Optional[int] = None, **kwargs):
@@ -352,13 +361,17 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
         prepare_multimodal_inputs runs ONCE per clip, the questions are embedded with embed_tokens; clips whose shared parts come out at the
         same length decode together (the engine takes one prefix length per call).  Returns one id tensor per clip, [questions, n]: row g is
         what generate() returns for the ids cat(shared, question g), within the decoder's bf16 tolerance (with output_first_logits=True:
-        (ids, fp32 logits of the first generated position))."""
+        (ids, fp32 logits of the first generated position)).
+        allowed_sequences / allowed_set: closed-set generation as in generate(); allowed_set is one list per clip with one set index per question."""
         for k in ("output_logits", "return_dict_in_generate", "inputs_embeds"):
             if kwargs.get(k) is not None and kwargs.get(k) is not False:
                 raise NotImplementedError(f"generate_questions returns token ids only: {k} is a generate() argument")
         want_first = bool(kwargs.get("output_first_logits"))
         self._check_generate_kwargs(kwargs)
         sampling = self._sampling(kwargs)
+        constraint = self._constraint(kwargs)
+        if constraint is not None and constraint[1] is not None and len(constraint[1]) != len(clips):
+            raise ValueError(f"allowed_set: {len(constraint[1])} lists of set indices for {len(clips)} clips")
         if ops.PROFILER is not None:
             ops.PROFILER.mark("encode_begin")
         prefixes, questions = [], []
@@ -379,7 +392,9 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
                                                       int(kwargs.get("max_new_tokens", 20)), eos_token_id=eos, pad_token_id=pad,
                                                       min_new_tokens=int(kwargs.get("min_new_tokens", 0) or 0), use_graph=kwargs.get("use_graph", True),
                                                       sampling=sampling, return_first_logits=want_first, kv_cache_dtype=kwargs.get("kv_cache_dtype"),
-                                                      weight_dtype=kwargs.get("weight_dtype"), max_rows=max_rows)
+                                                      weight_dtype=kwargs.get("weight_dtype"), max_rows=max_rows,
+                                                      constraint=None if constraint is None else
+                                                      (constraint[0], None if constraint[1] is None else [constraint[1][i] for i in idx]))
             for i, r in zip(idx, res):
                 outs[i] = r
         return outs
@@ -404,6 +419,20 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
                                       "it would change the decoded ids, so it is refused rather than ignored")
         if "max_length" in kwargs and kwargs.get("max_length") is not None and kwargs.get("max_new_tokens") is None:
             raise NotImplementedError("generate(max_length=...): with inputs_embeds only HF counts new tokens alone - pass max_new_tokens")
+
+    def _constraint(self, kwargs):
+        """allowed_sequences / allowed_set -> the engine's constraint argument (TokenTrie, set indices) or None.  eos_token_id and
+        min_new_tokens are checked against the trie here, before any device work (ValueError by name)."""
+        seqs = kwargs.get("allowed_sequences")
+        if seqs is None:
+            if kwargs.get("allowed_set") is not None:
+                raise ValueError("allowed_set names answer sets of allowed_sequences, which is missing")
+            return None
+        from .constrain import as_trie
+        trie = as_trie(seqs, self.lm_head.weight.shape[0], kwargs.get("eos_token_id", self.config.eos_token_id), int(kwargs.get("min_new_tokens", 0) or 0))
+        if kwargs.get("allowed_set") is None and trie.n_sets > 1:
+            raise ValueError(f"allowed_sequences holds {trie.n_sets} sets, so every row needs a set index: pass allowed_set")
+        return (trie, kwargs.get("allowed_set"))
 
     @staticmethod
     def _sampling(kwargs):

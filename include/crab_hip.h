@@ -416,6 +416,24 @@ int crab_advance(crab_ctx* ctx, void* stream, int32_t* pos_dev, int32_t* step_de
 int crab_sample_select(crab_ctx* ctx, void* stream, const float* logits, int64_t ldl, int B, int V, int64_t* cur_ids,
                        int64_t* out_ids, int64_t ld_out, const int32_t* step_dev, int32_t* finished, int eos_id, int pad_id,
                        int min_new_tokens, float temperature, int top_k, float top_p, uint64_t seed);
+/* The same step CONSTRAINED to a closed set of answers (csrc/constrain.hip): what HF does with PrefixConstrainedLogitsProcessor
+ * (generation/logits_process.py: every token prefix_allowed_tokens_fn does not return is set to -inf) - without the host callback, which cannot run
+ * between two replays of a captured step.  The answers are a token trie in CSR form (crab_amd/constrain.py): node n has the out-edges
+ * edge_off[n] .. edge_off[n + 1] - 1, edge e carries token edge_tok[e] (ascending within a node) and leads to node edge_dst[e]; an end of
+ * sequence owns an EOS edge to a sink node without edges.  node[b] (in/out) is the node row b stands on.  Per row: the allowed set is the
+ * tokens of the node's edges, minus EOS while step < min_new_tokens (HF order: MinNewTokensLength and PrefixConstrained mask first, the
+ * warpers see what is left); temperature == 0 takes the allowed token with the largest logit (on equal values the lowest id: the first-maximum
+ * rule of crab_greedy_select), temperature > 0 runs crab_sample_select's algorithm (temperature -> top_k -> top_p -> draw keyed by (seed,
+ * step_dev[0], row)) over the allowed tokens in ascending id order; then node[b] = edge_dst[e], cur_ids[b] = out_ids[b, step] = tok,
+ * finished[b] |= (tok == eos).  A finished row emits pad_id and keeps its node; a row with nothing allowed (the sink) emits pad_id and sets
+ * finished[b].  A node whose edges are all V tokens in order gives exactly crab_greedy_select / crab_sample_select.  The logits are read only
+ * through the edge list and never written.  Every index read from device memory is clamped against n_nodes / n_edges / V: a bad entry counts as
+ * "not allowed".  CRAB_E_INVALID for null operands, B / V / n_nodes / n_edges < 1, temperature < 0, top_p outside (0, 1], top_k < 0.
+ * ADDED under ABI 13 (crab_abi_version() still returns 13: nothing that existed changed); probe for the symbol, not for a version number. */
+int crab_constrained_select(crab_ctx* ctx, void* stream, const float* logits, int64_t ldl, int B, int V, const int32_t* edge_off,
+                            const int32_t* edge_tok, const int32_t* edge_dst, int n_nodes, int n_edges, int32_t* node, int64_t* cur_ids,
+                            int64_t* out_ids, int64_t ld_out, const int32_t* step_dev, int32_t* finished, int eos_id, int pad_id,
+                            int min_new_tokens, float temperature, int top_k, float top_p, uint64_t seed);
 
 /* ---------------------------------------------------------------------------------------------
  * Teacher-forced scoring (csrc/xent.hip): the language-model loss of models/modeling_llama.py:1261-1274 as reached from
