@@ -14,6 +14,7 @@
 // per key row, fp32 online softmax, cross-group merge through LDS.
 #include "common.h"
 #include "crab_internal.h"
+#include "attn_decode_core.h"
 #include <math.h>
 #include <stdlib.h>
 
@@ -461,17 +462,14 @@ __global__ __launch_bounds__(256, 2) void attn_fwd32_kernel(AttnP p) {
 
 // ---------------------------------------------------------------------------------------------- decode
 // block = 256 threads = 16 groups of 16 lanes; group gidx handles keys gidx, gidx+16, ...; each lane owns
-// EPL = HD/16 consecutive head-dim elements.  Every K / V row is read exactly once per step by exactly one block, so the
-// loads carry the non-temporal hint (global_load ... nt): measured 562 -> 537 us per launch in the benchmark (6.2 -> 6.5 TB/s;
-// 6.8 TB/s in isolation) - the stream no longer displaces the weights and activations the neighbouring GEMMs keep in L2 / MALL.
+// EPL = HD/16 consecutive head-dim elements.  The streaming loop (non-temporal loads, two keys per trip at HD = 128) and the merge of the
+// groups are dec_stream (HD = 128) / dec_group_merge (attn_decode_core.h), shared with the other one-query-per-row decode kernels.
 template <int HD>
 __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restrict__ q, long ldq, const bf16_t* __restrict__ kc,
                                                           const bf16_t* __restrict__ vc, bf16_t* __restrict__ o, long ldo, int H, int Hk,
                                                           int Tmax, int ctx_host, const int* __restrict__ ctx_dev, float scale,
                                                           const int* __restrict__ kv_start) {
     constexpr int EPL = HD / 16;
-    __shared__ float sm[16], sl[16];
-    __shared__ float so[16][HD];
     const int tid = threadIdx.x;
     const int grp = tid >> 4, sub = tid & 15;
     const int b = blockIdx.y, h = blockIdx.x;
@@ -487,88 +485,32 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
     float m = -1e30f, l = 0.f, acc[EPL];
 #pragma unroll
     for (int e = 0; e < EPL; ++e) acc[e] = 0.f;
-
-    if (EPL == 8) {
-        // TWO keys per trip (j and j + 16) with the next pair requested before the current one is consumed: every lane keeps four
-        // 16-byte K and four 16-byte V loads in flight, and the loop-carried online-softmax chain (max, two exps, rescale of the
-        // accumulators) is paid once per two keys
-        const u32x4 z4 = {0u, 0u, 0u, 0u};
-        u32x4 k0 = z4, v0 = z4, k1 = z4, v1 = z4;
-        if (grp < ctx) {
-            k0 = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(kb + (long)grp * HD));
-            v0 = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(vb + (long)grp * HD));
-        }
-        if (grp + 16 < ctx) {
-            k1 = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(kb + (long)(grp + 16) * HD));
-            v1 = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(vb + (long)(grp + 16) * HD));
-        }
-        for (int j = grp; j < ctx; j += 32) {
-            u32x4 kn0 = z4, vn0 = z4, kn1 = z4, vn1 = z4;
-            if (j + 32 < ctx) {
-                kn0 = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(kb + (long)(j + 32) * HD));
-                vn0 = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(vb + (long)(j + 32) * HD));
-            }
-            if (j + 48 < ctx) {
-                kn1 = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(kb + (long)(j + 48) * HD));
-                vn1 = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(vb + (long)(j + 48) * HD));
-            }
-            float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                s0 += qv[2 * e] * lo_bf(k0[e]) + qv[2 * e + 1] * hi_bf(k0[e]);
-                s1 += qv[2 * e] * lo_bf(k1[e]) + qv[2 * e + 1] * hi_bf(k1[e]);
-            }
-            s0 = row16_sum(s0); s1 = row16_sum(s1);
-            const bool has1 = j + 16 < ctx;                      // group-uniform
-            const float mn = fmaxf(m, has1 ? fmaxf(s0, s1) : s0);
-            const float a = __expf(m - mn), p0 = __expf(s0 - mn), p1 = has1 ? __expf(s1 - mn) : 0.f;
-            l = l * a + (p0 + p1);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                acc[2 * e] = acc[2 * e] * a + (p0 * lo_bf(v0[e]) + p1 * lo_bf(v1[e]));
-                acc[2 * e + 1] = acc[2 * e + 1] * a + (p0 * hi_bf(v0[e]) + p1 * hi_bf(v1[e]));
-            }
-            m = mn;
-            k0 = kn0; v0 = vn0; k1 = kn1; v1 = vn1;
-        }
+    if constexpr (EPL == 8) {
+        dec_stream(qv, kb, vb, ctx, grp, m, l, acc);
     } else {
-    for (int j = grp; j < ctx; j += 16) {
-        float kx[EPL], vx[EPL];
-        {
-            u32x2 kw = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(kb + (long)j * HD));
-            u32x2 vw = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(vb + (long)j * HD));
+        // HD = 64 (the tiny test models): one key per trip, the dot summed element by element.  Kept here, not in the header: moved into dec_stream
+        // the compiler fused the other product of acc * a + pw * v and outputs differed from before in the last bit (scripts/ab_bits.py, volume cases)
+        for (int j = grp; j < ctx; j += 16) {
+            float kx[EPL], vx[EPL];
+            const u32x2 kw = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(kb + (long)j * HD));
+            const u32x2 vw = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(vb + (long)j * HD));
 #pragma unroll
             for (int e = 0; e < 2; ++e) { kx[2 * e] = lo_bf(kw[e]); kx[2 * e + 1] = hi_bf(kw[e]); vx[2 * e] = lo_bf(vw[e]); vx[2 * e + 1] = hi_bf(vw[e]); }
+            float sdot = 0.f;
+#pragma unroll
+            for (int e = 0; e < EPL; ++e) sdot += qv[e] * kx[e];
+            sdot = row16_sum(sdot);
+            const float mn = fmaxf(m, sdot);
+            const float a = __expf(m - mn), pw = __expf(sdot - mn);
+            l = l * a + pw;
+#pragma unroll
+            for (int e = 0; e < EPL; ++e) acc[e] = acc[e] * a + pw * vx[e];
+            m = mn;
         }
-        float sdot = 0.f;
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) sdot += qv[e] * kx[e];
-        sdot = row16_sum(sdot);
-        float mn = fmaxf(m, sdot);
-        float a = __expf(m - mn), pw = __expf(sdot - mn);
-        l = l * a + pw;
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) acc[e] = acc[e] * a + pw * vx[e];
-        m = mn;
     }
-    }
-    if (sub == 0) { sm[grp] = m; sl[grp] = l; }
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) so[grp][sub * EPL + e] = acc[e];
-    __syncthreads();
-    if (tid < HD) {
-        float M = -1e30f;
-#pragma unroll
-        for (int g = 0; g < 16; ++g) M = fmaxf(M, sm[g]);
-        float L = 0.f, O = 0.f;
-#pragma unroll
-        for (int g = 0; g < 16; ++g) {
-            float w = __expf(sm[g] - M);
-            L += sl[g] * w;
-            O += so[g][tid] * w;
-        }
-        o[(long)b * ldo + (long)h * HD + tid] = f2bf(O / L);
-    }
+    float M, L, O;
+    dec_group_merge<HD, 16, EPL>(grp, sub, m, l, acc, M, L, O);
+    if (tid < HD) o[(long)b * ldo + (long)h * HD + tid] = f2bf(O / L);
 }
 
 
@@ -583,8 +525,6 @@ __global__ __launch_bounds__(256) void attn_decode_keymask_kernel(const bf16_t* 
                                                                   int Tmax, int ctx_host, const int* __restrict__ ctx_dev, float scale,
                                                                   const uint32_t* __restrict__ key_mask, long key_mask_ld) {
     constexpr int EPL = HD / 16, WPL = EPL / 2;
-    __shared__ float sm[16], sl[16];
-    __shared__ float so[16][HD];
     const int tid = threadIdx.x;
     const int grp = tid >> 4, sub = tid & 15;
     const int b = blockIdx.y, h = blockIdx.x;
@@ -602,6 +542,8 @@ __global__ __launch_bounds__(256) void attn_decode_keymask_kernel(const bf16_t* 
     for (int e = 0; e < EPL; ++e) acc[e] = 0.f;
     for (int j = grp; j < ctx; j += 16) {
         if (!((km[j >> 5] >> (j & 31)) & 1u)) continue;          // group-uniform
+        // the one-key step, at its site: as a helper shared with the rope kernel's d = 64 loop the compiler fused the other product of
+        // acc * a + pw * v and 8-39 outputs per 128 x 32 rows moved by a bf16 ulp ("One decode-attention core")
         uint32_t kw[WPL], vw[WPL];
 #pragma unroll
         for (int w = 0; w < WPL; ++w) {
@@ -622,23 +564,9 @@ __global__ __launch_bounds__(256) void attn_decode_keymask_kernel(const bf16_t* 
         }
         m = mn;
     }
-    if (sub == 0) { sm[grp] = m; sl[grp] = l; }
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) so[grp][sub * EPL + e] = acc[e];
-    __syncthreads();
-    if (tid < HD) {
-        float M = -1e30f;
-#pragma unroll
-        for (int g = 0; g < 16; ++g) M = fmaxf(M, sm[g]);
-        float L = 0.f, O = 0.f;
-#pragma unroll
-        for (int g = 0; g < 16; ++g) {
-            const float w = __expf(sm[g] - M);
-            L += sl[g] * w;
-            O += so[g][tid] * w;
-        }
-        o[(long)b * ldo + (long)h * HD + tid] = f2bf(L > 0.f ? O / L : 0.f);     // no visible key at all (a pad row): zeros, like the prefill kernels
-    }
+    float M, L, O;
+    dec_group_merge<HD, 16, EPL>(grp, sub, m, l, acc, M, L, O);
+    if (tid < HD) o[(long)b * ldo + (long)h * HD + tid] = f2bf(L > 0.f ? O / L : 0.f);     // no visible key at all (a pad row): zeros, like the prefill kernels
 }
 
 
@@ -661,8 +589,6 @@ __global__ __launch_bounds__(NG * 16) void attn_decode_rope_kernel(const bf16_t*
                                                                int H, int Hk, int Tmax, int pos0, const int* __restrict__ pos_dev, float scale,
                                                                float* part, unsigned* counters) {
     constexpr int EPL = HD / 16, WPL = EPL / 2;                 // elements / 32-bit words per lane
-    __shared__ float sm[NG], sl[NG];
-    __shared__ float so[NG][HD];
     __shared__ unsigned s_old;
     const int tid = threadIdx.x;
     const int grp = tid >> 4, sub = tid & 15;
@@ -748,7 +674,7 @@ __global__ __launch_bounds__(NG * 16) void attn_decode_rope_kernel(const bf16_t*
             float sc[NB], mx = -1e30f;
 #pragma unroll
             for (int u = 0; u < NB; ++u) {
-                float d = 0.f;
+                float d = 0.f;                                   // dec_dot's sum, spelled out: through the helper the 512-thread form takes 209 VGPRs, not 126
 #pragma unroll
                 for (int e = 0; e < 4; ++e) d += qv[2 * e] * lo_bf(kk[u][e]) + qv[2 * e + 1] * hi_bf(kk[u][e]);
                 d = row16_sum(d);
@@ -778,6 +704,7 @@ __global__ __launch_bounds__(NG * 16) void attn_decode_rope_kernel(const bf16_t*
             m = mn;
         }
     } else {
+    // (the one-key step of the keymask kernel, kept here for the same reason: shared, its bits moved)
     for (int j = grp; j < nc; j += NG) {
         uint32_t kk2[WPL], vv2[WPL];
 #pragma unroll
@@ -801,7 +728,7 @@ __global__ __launch_bounds__(NG * 16) void attn_decode_rope_kernel(const bf16_t*
     }
     }
     {
-        float sdot = 0.f;
+        float sdot = 0.f;                                        // element by element, not dec_dot's pair order: the bits this step has always had
 #pragma unroll
         for (int e = 0; e < EPL; ++e) sdot += qv[e] * kn[e];
         sdot = row16_sum(sdot);
@@ -814,21 +741,8 @@ __global__ __launch_bounds__(NG * 16) void attn_decode_rope_kernel(const bf16_t*
             m = mn;
         }
     }
-    if (sub == 0) { sm[grp] = m; sl[grp] = l; }
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) so[grp][sub * EPL + e] = acc[e];
-    __syncthreads();
-    float Mx = -1e30f, L = 0.f, O = 0.f;
-    if (tid < HD) {
-#pragma unroll
-        for (int g = 0; g < NG; ++g) Mx = fmaxf(Mx, sm[g]);
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-            const float w = __expf(sm[g] - Mx);
-            L += sl[g] * w;
-            O += so[g][tid] * w;
-        }
-    }
+    float Mx, L, O;
+    dec_group_merge<HD, NG, EPL>(grp, sub, m, l, acc, Mx, L, O);
     if (nsplit == 1) {
         if (tid < HD) o[(long)b * ldo + (long)h * HD + tid] = f2bf(O / L);
         return;

@@ -6,12 +6,14 @@
 //       heads of the kv head: the (row, head) pairs are the rows of the MFMA A operand, as attn_decode_gqa_kernel (attn.hip) puts its heads there -
 //       H == Hk: 16 sibling rows, H / Hk == 7: two siblings x 7 heads.  All P prefix keys are visible to every query (every query sits at a position
 //       >= P).  Output per (query row, head), fp32, into the caller's workspace: the unnormalised o[d], the running max m and the sum l.
-//   attn_own_merge_row_kernel (K2, H == Hk, one query per row)  attn_decode_kernel's schedule (attn.hip) over the row's own keys, then the merge.
+//   attn_own_merge_row_kernel (K2, H == Hk, one query per row)  attn_decode_kernel (attn.hip) over the row's own keys, from the same streaming loop
+//       (HD = 128; the HD = 64 loop is a copy) and group merge (attn_decode_core.h), then the merge.
 //   attn_own_merge_kernel (K2, every other form)  one block per (row, kv head, query index): the H / Hk heads as A-operand rows over the own keys -
 //       every own K / V row is read once per kv head - then the merge.
 // The merge is the log-sum-exp rule in a fixed order (own part, then prefix part): the result is a function of the inputs alone, no atomics, no tickets.
 #include "common.h"
 #include "crab_internal.h"
+#include "attn_decode_core.h"
 #include <math.h>
 
 namespace {
@@ -262,16 +264,15 @@ __global__ __launch_bounds__(256, 2) void attn_own_merge_kernel(const bf16_t* __
     }
 }
 
-// K2, H == Hk and one query per row: the load schedule of attn_decode_kernel (attn.hip; 16 groups of 16 lanes, group g takes keys g, g + 16, ...,
-// two keys per trip with the next pair in flight at HD = 128), then the merge with the prefix partial.  grid (H, B).
+// K2, H == Hk and one query per row: attn_decode_kernel (attn.hip) over the row's own keys - the same dec_stream / dec_group_merge
+// (attn_decode_core.h: 16 groups of 16 lanes, group g takes keys g, g + 16, ..., two keys per trip with the next pair in flight at HD = 128) behind
+// this kernel's own clamps of kv_start and ctx - then the merge with the prefix partial instead of the plain O / L.  grid (H, B).
 template <int HD>
 __global__ __launch_bounds__(256) void attn_own_merge_row_kernel(const bf16_t* __restrict__ q, long ldq, const float* __restrict__ ws,
                                                                  const bf16_t* __restrict__ kc, const bf16_t* __restrict__ vc,
                                                                  bf16_t* __restrict__ o, long ldo, int H, int Tmax, int ctx_host,
                                                                  const int* __restrict__ ctx_dev, float scale, const int* __restrict__ kv_start) {
     constexpr int EPL = HD / 16;
-    __shared__ float sm[16], sl[16];
-    __shared__ float so[16][HD];
     const int tid = threadIdx.x;
     const int grp = tid >> 4, sub = tid & 15;
     const int b = blockIdx.y, h = blockIdx.x;
@@ -286,48 +287,11 @@ __global__ __launch_bounds__(256) void attn_own_merge_row_kernel(const bf16_t* _
     float m = -1e30f, l = 0.f, acc[EPL];
 #pragma unroll
     for (int e = 0; e < EPL; ++e) acc[e] = 0.f;
-
-    if (EPL == 8) {
-        const u32x4 z4 = {0u, 0u, 0u, 0u};
-        u32x4 k0 = z4, v0 = z4, k1 = z4, v1 = z4;
-        if (grp < ctx) {
-            k0 = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(kb + (long)grp * HD));
-            v0 = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(vb + (long)grp * HD));
-        }
-        if (grp + 16 < ctx) {
-            k1 = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(kb + (long)(grp + 16) * HD));
-            v1 = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(vb + (long)(grp + 16) * HD));
-        }
-        for (int j = grp; j < ctx; j += 32) {
-            u32x4 kn0 = z4, vn0 = z4, kn1 = z4, vn1 = z4;
-            if (j + 32 < ctx) {
-                kn0 = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(kb + (long)(j + 32) * HD));
-                vn0 = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(vb + (long)(j + 32) * HD));
-            }
-            if (j + 48 < ctx) {
-                kn1 = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(kb + (long)(j + 48) * HD));
-                vn1 = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(vb + (long)(j + 48) * HD));
-            }
-            float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                s0 += qv[2 * e] * lo_bf(k0[e]) + qv[2 * e + 1] * hi_bf(k0[e]);
-                s1 += qv[2 * e] * lo_bf(k1[e]) + qv[2 * e + 1] * hi_bf(k1[e]);
-            }
-            s0 = row16_sum(s0); s1 = row16_sum(s1);
-            const bool has1 = j + 16 < ctx;                      // group-uniform
-            const float mn = fmaxf(m, has1 ? fmaxf(s0, s1) : s0);
-            const float a = __expf(m - mn), p0 = __expf(s0 - mn), p1 = has1 ? __expf(s1 - mn) : 0.f;
-            l = l * a + (p0 + p1);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                acc[2 * e] = acc[2 * e] * a + (p0 * lo_bf(v0[e]) + p1 * lo_bf(v1[e]));
-                acc[2 * e + 1] = acc[2 * e + 1] * a + (p0 * hi_bf(v0[e]) + p1 * hi_bf(v1[e]));
-            }
-            m = mn;
-            k0 = kn0; v0 = vn0; k1 = kn1; v1 = vn1;
-        }
+    if constexpr (EPL == 8) {
+        dec_stream(qv, kb, vb, ctx, grp, m, l, acc);
     } else {
+        // HD = 64 (the tiny test models): one key per trip, the dot summed element by element.  Kept here, not in the header: moved into dec_stream
+        // the compiler fused the other product of acc * a + pw * v and outputs differed from before in the last bit (scripts/ab_bits.py, volume cases)
         for (int j = grp; j < ctx; j += 16) {
             float kx[EPL], vx[EPL];
             const u32x2 kw = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(kb + (long)j * HD));
@@ -346,21 +310,9 @@ __global__ __launch_bounds__(256) void attn_own_merge_row_kernel(const bf16_t* _
             m = mn;
         }
     }
-    if (sub == 0) { sm[grp] = m; sl[grp] = l; }
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) so[grp][sub * EPL + e] = acc[e];
-    __syncthreads();
+    float M, L, O;
+    dec_group_merge<HD, 16, EPL>(grp, sub, m, l, acc, M, L, O);
     if (tid < HD) {
-        float M = -1e30f;
-#pragma unroll
-        for (int g = 0; g < 16; ++g) M = fmaxf(M, sm[g]);
-        float L = 0.f, O = 0.f;
-#pragma unroll
-        for (int g = 0; g < 16; ++g) {                          // group order: a key group without keys (m = -1e30, l = 0) adds nothing
-            const float w = __expf(sm[g] - M);
-            L += sl[g] * w;
-            O += so[g][tid] * w;
-        }
         const float* w = ws + ((long)b * H + h) * (HD + 2);
         o[(long)b * ldo + (long)h * HD + tid] = f2bf(px_merge(M, L, O, w[HD], w[HD + 1], w[tid]));
     }

@@ -10,7 +10,7 @@ mkdir -p build
 pids=()
 for f in *.hip; do
   o=build/${f%.hip}.o
-  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ common.h -nt "$o" ] || [ crab_internal.h -nt "$o" ] || [ fp8_common.h -nt "$o" ] || [ gemm_epilogue.h -nt "$o" ] || [ build.sh -nt "$o" ] || [ ../../include/crab_hip.h -nt "$o" ]; then
+  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ common.h -nt "$o" ] || [ crab_internal.h -nt "$o" ] || [ fp8_common.h -nt "$o" ] || [ gemm_epilogue.h -nt "$o" ] || [ attn_decode_core.h -nt "$o" ] || [ build.sh -nt "$o" ] || [ ../../include/crab_hip.h -nt "$o" ]; then
     extra=""
     # attn.hip: keep the MFMA accumulators in VGPRs.  The flash kernels rescale O every K/V tile; with AGPR accumulators that is
     # 32 v_accvgpr_read + 32 v_mov around 32 multiplies per tile (CLIP shape 150 -> 126 us, decoder shape 217 -> 213 us)

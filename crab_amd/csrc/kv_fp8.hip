@@ -19,6 +19,7 @@
 // instruction, round to nearest even, word select for the upper half).  Everything written to memory is a plain vector store.
 #include "common.h"
 #include "crab_internal.h"
+#include "attn_decode_core.h"
 #include "fp8_common.h"                     // kv8_scale, pack_fp8x4: the row format, shared with the FP8 decoder weights
 
 namespace {
@@ -87,7 +88,9 @@ __global__ __launch_bounds__(256) void kv_quant_fp8_kernel(const bf16_t* __restr
 // EPL = HD / 8 consecutive head-dim elements = EPL bytes of a row (HD = 128: one 16-byte load per lane and row, as many bytes in flight
 // per wave as attn_decode_kernel keeps).  The row scales are folded in as scalars: score = (q . codes) * k_scale, and v_scale rides on
 // the softmax weight - nothing is scaled element-wise.  Two keys per trip with the next pair requested before the current one is
-// consumed, non-temporal loads (every row is read once per step by one block; the G blocks of a grouped-query KV head meet in L2).
+// consumed, non-temporal loads (every row is read once per step by one block; the G blocks of a grouped-query KV head meet in L2): the
+// schedule of dec_stream (attn_decode_core.h) over codes and row scales instead of bf16 words, so the loop is this kernel's own; the merge
+// of the 32 groups is dec_group_merge of that header.
 // From the RAW q|k|v row (the projection ran without RoPE): q and the new k rotate here at position pos - kv_start (lane sub's partner
 // dim +- d/2 is lane sub ^ 4), are rounded to bf16 like the stored form, the new k / v rows are quantised exactly like the quantiser
 // above; the block with h % G == 0 appends codes and scales at slot pos, and EVERY block attends the dequantised new row (group 0 seeds
@@ -104,8 +107,6 @@ __global__ __launch_bounds__(256) void attn_decode_fp8_kernel(const bf16_t* __re
                                                               const int* __restrict__ kv_start) {
     constexpr int NG = 32, EPL = HD / 8, WPL = EPL / 4;                   // elements, fp8 words per lane
     typedef typename CodeVec<WPL>::type cvec;
-    __shared__ float sm[NG], sl[NG];
-    __shared__ float so[NG][HD];
     __shared__ float snew[3][HD];                               // q | new k | new v of this head, fp32 of the bf16-rounded values
     const int tid = threadIdx.x;
     const int grp = tid >> 3, sub = tid & 7;
@@ -234,23 +235,12 @@ __global__ __launch_bounds__(256) void attn_decode_fp8_kernel(const bf16_t* __re
     }
 #undef KV8_DOT
 #undef KV8_ACC
-    if (sub == 0) { sm[grp] = m; sl[grp] = l; }
+    // (one VGPR fewer than with the merge written here, 98 / 66 at HD = 128 / 64; LDS and occupancy as before)
+    float accf[EPL], M, L, O;
 #pragma unroll
-    for (int e = 0; e < EPL / 2; ++e) { so[grp][sub * EPL + 2 * e] = acc[e][0]; so[grp][sub * EPL + 2 * e + 1] = acc[e][1]; }
-    __syncthreads();
-    if (tid < HD) {
-        float M = -1e30f;
-#pragma unroll
-        for (int g = 0; g < NG; ++g) M = fmaxf(M, sm[g]);
-        float Lsum = 0.f, O = 0.f;
-#pragma unroll 4
-        for (int g = 0; g < NG; ++g) {
-            const float w = __expf(sm[g] - M);
-            Lsum += sl[g] * w;
-            O += so[g][tid] * w;
-        }
-        o[(long)b * ldo + (long)h * HD + tid] = f2bf(O / Lsum);
-    }
+    for (int e = 0; e < EPL / 2; ++e) { accf[2 * e] = acc[e][0]; accf[2 * e + 1] = acc[e][1]; }
+    dec_group_merge<HD, NG, EPL, 4>(grp, sub, m, l, accf, M, L, O);
+    if (tid < HD) o[(long)b * ldo + (long)h * HD + tid] = f2bf(O / L);
 }
 
 }  // namespace

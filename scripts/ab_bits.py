@@ -1,9 +1,14 @@
-"""Bit-compare two builds of libcrab_hip.so on the decode GEMMs (csrc/skinny.hip and the split-K reduction of csrc/gemm.hip).
+"""Bit-compare two builds of libcrab_hip.so on the decode GEMMs (csrc/skinny.hip and the split-K reduction of csrc/gemm.hip) and on the decode
+attention kernels (csrc/attn_decode_core.h and its users in attn.hip, attn_prefix.hip, kv_fp8.hip).
 
-    python scripts/ab_bits.py <a.so> <b.so>
+    python scripts/ab_bits.py <a.so> <b.so> [gemm | attn]
 
-One fresh child process per library (CRAB_HIP_LIB, crab_amd/_lib.py) runs the launch list below on seeded inputs and saves every output
-tensor; the parent compares the two sets with torch.equal and prints the first case that differs.  Exit status 0: every case identical."""
+One fresh child process per library (CRAB_HIP_LIB, crab_amd/_lib.py) runs the launch lists below (both, or the one named) on seeded inputs and
+saves every output tensor; the parent compares the two sets with torch.equal and prints every case that differs.  Exit status 0: every
+case identical.  The attention cases are one or two launches each (edge cases), followed by "volume" cases of 128 x 32 rows per
+launch: the kernels write a * b + c * d, which product gets fused is the compiler's choice per build, and the last fp32 bit this moves reaches
+about one bf16 output in 10^4 - the edge cases alone pass such a build.  Cache rows outside the visible range hold NaN, and outputs are
+compared as bit patterns (a NaN that reaches an output must be the same NaN)."""
 import os
 import subprocess
 import sys
@@ -91,31 +96,176 @@ def _cases():
                           lambda: ops.gemm(p["x"], p["w"], bias=p["bias"], act="swiglu_pair", out_fp32=f32, tune=tune, **p["seg2"]))
 
 
+KEYS = (1, 15, 16, 17, 31, 32, 33, 47, 48, 49, 65, 97)                      # visible keys per row: the 16-key group and 32-key prefetch edges
+NAN = float("nan")
+
+
+def _bits(t):
+    return t.view({BF: torch.int16, torch.float32: torch.int32}.get(t.dtype, t.dtype)).cpu()
+
+
+def _attn_cases():
+    """Yields (name, tensors) for the one-query-per-row decode attention kernels, with the grouped (MFMA) kernels of the same files as controls."""
+    from crab_amd import ops
+
+    def run(name, fn):
+        out = fn()
+        torch.cuda.synchronize()
+        return "attn " + name, [_bits(t) for t in (out if isinstance(out, (list, tuple)) else [out])]
+
+    def i32(v):
+        return torch.tensor(v, dtype=torch.int32, device="cuda")
+
+    base = {}
+
+    def cache(B, Hk, Tmax, d, lo, hi, seed):
+        """K / V with random rows lo[b] .. hi - 1 and NaN everywhere else."""
+        key = (B, Hk, Tmax, d, seed)
+        if key not in base:
+            base.clear()                                                        # one shape at a time: the largest is 40 MB per tensor
+            base[key] = _rand(B, Hk, Tmax, d, seed=seed, scale=0.5), _rand(B, Hk, Tmax, d, seed=seed + 1)
+        kc, vc = base[key]
+        t = torch.arange(Tmax, device="cuda")[None, :]
+        dead = ((t < i32(lo)[:, None]) | (t >= hi))[:, None, :, None]
+        return kc.masked_fill(dead, NAN), vc.masked_fill(dead, NAN)
+
+    for d in (64, 128):
+        sc = d ** -0.5
+        # ---- attn_decode_kernel: a device ctx word, the key counts through kv_start; the same rows without kv_start
+        H, B, Tmax, ctx = 2, len(KEYS), 104, 97
+        q = _rand(B, H * d, seed=10 + d)
+        word = i32([ctx - 5])
+        for name, lo in (("kv_start", [ctx - n for n in KEYS]), ("no kv_start", [0] * B)):
+            kc, vc = cache(B, H, Tmax, d, lo, ctx, seed=20)
+            ks = i32(lo) if name == "kv_start" else None
+            yield run(f"decode d={d} {name}", lambda: ops.attn_decode(q, kc, vc, torch.zeros_like(q), B, H, H, d, Tmax, 5, sc, ctx_dev=word, kv_start=ks))
+        # ---- attn_decode_keymask_kernel: a random mask over the 97 rows (the hidden rows poisoned too), row 3 fully masked
+        vis = torch.rand(B, ctx, generator=torch.Generator().manual_seed(30)).cuda() < 0.6
+        vis[3] = False
+        kc, vc = cache(B, H, Tmax, d, [0] * B, ctx, seed=20)
+        hide = ~torch.nn.functional.pad(vis, (0, Tmax - ctx))[:, None, :, None]
+        kc, vc = kc.masked_fill(hide, NAN), vc.masked_fill(hide, NAN)
+        km = ops.pack_key_mask(torch.nn.functional.pad(vis, (0, Tmax - ctx)))
+        yield run(f"keymask d={d} host ctx", lambda: ops.attn_decode(q, kc, vc, torch.zeros_like(q), B, H, H, d, Tmax, ctx, sc, key_mask=km))
+        yield run(f"keymask d={d} device ctx", lambda: ops.attn_decode(q, kc, vc, torch.zeros_like(q), B, H, H, d, Tmax, 5, sc, ctx_dev=word, key_mask=km))
+        # ---- attn_decode_rope_kernel: 8 splits | 2 splits (d = 128: the 512-thread kernel) | 1 split; one workspace over all positions
+        for B, H, Hk in ((2, 2, 2), (8, 32, 8), (16, 32, 8)):
+            Tmax = 304
+            tab = ops.rope_table(Tmax, d, 10000.0, "cuda")
+            ws = ops.attn_decode_rope_workspace(B, H, d, "cuda")
+            qkv = _rand(B, (H + 2 * Hk) * d, seed=40 + d)
+            for pos in (0, 1, 127, 128, 129, 255, 256, 257, 300):
+                def rope():
+                    k0, v0 = cache(B, Hk, Tmax, d, [0] * B, pos, seed=50)
+                    kc, vc = k0.clone(), v0.clone()
+                    o = ops.attn_decode_rope(qkv, tab, kc, vc, torch.zeros(B, H * d, dtype=BF, device="cuda"), B, H, Hk, d, Tmax, pos, sc, workspace=ws)
+                    keep = torch.arange(Tmax, device="cuda") != pos              # both caches: the appended rows, and that no other row changed
+                    same = torch.tensor([torch.equal(a[:, :, keep].view(torch.int16), b[:, :, keep].view(torch.int16)) for a, b in ((kc, k0), (vc, v0))])
+                    return o, kc[:, :, pos].contiguous(), vc[:, :, pos].contiguous(), same, ws.clone()        # ws: the fp32 partials of the splits
+                yield run(f"rope d={d} B={B} H={H} pos={pos}", rope)
+        # ---- attn_decode_fp8_kernel: n cached keys in front of the slot being decoded
+        B, H, Hk, Tmax = 2, 4, 2, 104
+        tab = ops.rope_table(Tmax, d, 10000.0, "cuda")
+        qkv = _rand(B, (H + 2 * Hk) * d, seed=60 + d)
+        for n in (0, 1, 31, 32, 33, 63, 64, 65, 97):
+            for ks0 in (0, 3):
+                def fp8():
+                    pos = ks0 + n
+                    src_k, src_v = _rand(1, B, Hk, Tmax, d, seed=70, scale=0.5), _rand(1, B, Hk, Tmax, d, seed=71)
+                    codes = [torch.full((1, B, Hk, Tmax, d), 0x7F, dtype=torch.uint8, device="cuda") for _ in range(2)]      # 0x7f: the e4m3fn NaN
+                    scales = [torch.full((1, B, Hk, Tmax), NAN, dtype=torch.float32, device="cuda") for _ in range(2)]
+                    if n:
+                        ops.kv_quant_fp8(src_k, src_v, codes[0], codes[1], scales[0], scales[1], t0=ks0, t_dst=ks0, S=n)
+                    o = ops.attn_decode_fp8(qkv, tab, codes[0][0], codes[1][0], scales[0][0], scales[1][0], torch.zeros(B, H * d, dtype=BF, device="cuda"),
+                                            B, H, Hk, d, Tmax, pos, sc, kv_start=i32([ks0] * B) if ks0 else None)
+                    return [o] + codes + scales
+                yield run(f"fp8 d={d} cached={n} kv_start={ks0}", fp8)
+        # ---- attn_prefix_partial + attn_own_merge: the row kernel (H == Hk, one query per row); (14, 2, 128): the grouped kernel, a control
+        for H, Hk in ((2, 2), (14, 2)) if d == 128 else ((2, 2),):
+            B, P, Tp, Tmax, kv0 = 3, 17, 24, 72, 3
+            q = _rand(B, H * d, seed=80 + d)
+            tiles, row_clip = ops.prefix_tile_plan([B], H, Hk)
+            pk, pv = cache(1, Hk, Tp, d, [0], P, seed=81)
+            for own in (1, 16, 17, 32, 33, 49, 65):
+                def prefix():
+                    ws = torch.zeros(ops.attn_prefix_bytes(B, H, d), dtype=torch.uint8, device="cuda")
+                    ops.attn_prefix_partial(q, pk, pv, ws, i32(tiles).reshape(-1), i32(row_clip), B, H, Hk, d, P, sc)
+                    kc, vc = cache(B, Hk, Tmax, d, [kv0] * B, kv0 + own, seed=82)
+                    o = ops.attn_own_merge(q, ws, kc, vc, torch.zeros_like(q), B, 1, H, Hk, d, Tmax, kv0 + own, sc, kv_start=i32([kv0] * B))
+                    return o, ws
+                yield run(f"prefix pair d={d} H={H} Hk={Hk} own={own}", prefix)
+    # ---- volume.  The kernels write a * b + c * d, and which product the compiler fuses is its choice per build: a build that chooses otherwise
+    # differs in the last fp32 bit, which reaches about one bf16 output in 10^4.  Enough rows per kernel that such a build cannot pass by luck.
+    for d in (64, 128):
+        sc = d ** -0.5
+        B, H, Tmax, ctx = 128, 32, 136, 131
+        gen = torch.Generator(device="cuda").manual_seed(100 + d)
+        rn = lambda *shape: (torch.randn(*shape, device="cuda", generator=gen) * 0.5).bfloat16()
+        kc, vc = rn(B, H, Tmax, d), rn(B, H, Tmax, d)
+        ks = i32([(7 * b) % 64 for b in range(B)])
+        km = ops.pack_key_mask(torch.rand(B, Tmax, device="cuda", generator=gen) < 0.7)
+        tab = ops.rope_table(Tmax, d, 10000.0, "cuda")
+        k8, v8 = (torch.empty(1, B, H, Tmax, d, dtype=torch.uint8, device="cuda") for _ in range(2))
+        s8k, s8v = (torch.empty(1, B, H, Tmax, dtype=torch.float32, device="cuda") for _ in range(2))
+        ops.kv_quant_fp8(kc[None], vc[None], k8, v8, s8k, s8v)
+        wss = {b: ops.attn_decode_rope_workspace(b, H, d, "cuda") for b in (1, 8)}
+        for r in range(4):
+            q, qkv = rn(B, H * d), rn(B, 3 * H * d)
+            o = lambda rows=B: torch.zeros(rows, H * d, dtype=BF, device="cuda")
+            part = torch.randn(B * H, d + 2, device="cuda", generator=gen)                  # a prefix partial: o, m, l > 0
+            part[:, d + 1] = part[:, d + 1].abs() + 0.5
+            yield run(f"volume d={d} #{r} decode", lambda: ops.attn_decode(q, kc, vc, o(), B, H, H, d, Tmax, ctx, sc, kv_start=ks))
+            yield run(f"volume d={d} #{r} keymask", lambda: ops.attn_decode(q, kc, vc, o(), B, H, H, d, Tmax, ctx, sc, key_mask=km))
+            yield run(f"volume d={d} #{r} own_merge", lambda: ops.attn_own_merge(q, part.view(torch.uint8).reshape(-1), kc, vc, o(), B, 1, H, H, d, Tmax, ctx, sc,
+                                                                              kv_start=ks))
+            yield run(f"volume d={d} #{r} rope", lambda: ops.attn_decode_rope(qkv, tab, kc, vc, o(), B, H, H, d, Tmax, ctx, sc))
+            for b in (1, 8):                                                                  # 8 and 2 splits: the fp32 partials are outputs too
+                yield run(f"volume d={d} #{r} rope B={b}", lambda: (ops.attn_decode_rope(qkv, tab, kc, vc, o(b), b, H, H, d, Tmax, ctx, sc, workspace=wss[b]),
+                                                                    wss[b].clone()))
+            yield run(f"volume d={d} #{r} fp8", lambda: ops.attn_decode_fp8(qkv, tab, k8[0], v8[0], s8k[0], s8v[0], o(), B, H, H, d, Tmax, ctx, sc, kv_start=ks))
+        del kc, vc, k8, v8
+    # ---- attn_decode through attn_decode_gqa_kernel<128, 4>: a control for a file that is recompiled
+    B, H, Hk, d, Tmax, ctx = 64, 16, 4, 128, 72, 70
+    q = _rand(B, H * d, seed=90)
+    lo = [(5 * b) % 40 for b in range(B)]
+    kc, vc = cache(B, Hk, Tmax, d, lo, ctx, seed=91)
+    yield run("decode grouped-query G=4", lambda: ops.attn_decode(q, kc, vc, torch.zeros_like(q), B, H, Hk, d, Tmax, ctx, d ** -0.5, kv_start=i32(lo)))
+
+
+LISTS = {"gemm": _cases, "attn": _attn_cases}
+
+
 def main():
-    if len(sys.argv) == 3 and sys.argv[1] == "--child":
+    if len(sys.argv) == 4 and sys.argv[1] == "--child":
         sys.path.insert(0, ROOT)
-        torch.save(dict(_cases()), sys.argv[2])
+        torch.save({k: v for which in sys.argv[3].split("+") for k, v in LISTS[which]()}, sys.argv[2])
         return 0
-    if len(sys.argv) != 3:
+    if len(sys.argv) not in (3, 4) or (len(sys.argv) == 4 and sys.argv[3] not in LISTS):
         print(__doc__)
         return 2
+    which = sys.argv[3] if len(sys.argv) == 4 else "gemm+attn"
     sets = []
     with tempfile.TemporaryDirectory() as tmp:
-        for i, lib in enumerate(sys.argv[1:]):
+        for i, lib in enumerate(sys.argv[1:3]):
             out = os.path.join(tmp, f"{i}.pt")
-            subprocess.run([sys.executable, os.path.abspath(__file__), "--child", out], check=True, env=dict(os.environ, CRAB_HIP_LIB=os.path.abspath(lib)))
+            subprocess.run([sys.executable, os.path.abspath(__file__), "--child", out, which], check=True,
+                           env=dict(os.environ, CRAB_HIP_LIB=os.path.abspath(lib)))
             sets.append(torch.load(out))
     a, b = sets
     assert list(a) == list(b) and len(a) > 0
     refused = [n for n in a if a[n][0].dtype == torch.uint8]
+    bad = 0
     for name in a:
         if len(a[name]) != len(b[name]) or not all(torch.equal(s, t) for s, t in zip(a[name], b[name])):
+            bad += 1
             print(f"DIFFERENT: {name}")
             for s, t in zip(a[name], b[name]):
                 if s.shape == t.shape and not torch.equal(s, t):
                     i = (s != t).nonzero()[0].tolist()
                     print(f"  first at {i}: {s[tuple(i)].item()} vs {t[tuple(i)].item()} ({(s != t).sum().item()} of {s.numel()} elements)")
-            return 1
+    if bad:
+        print(f"{bad} of {len(a)} cases differ")
+        return 1
     print(f"all {len(a)} cases identical ({sum(len(v) for v in a.values())} tensors; {len(refused)} calls refused by both libraries alike)")
     for msg in sorted({bytes(a[n][0].tolist()).decode() for n in refused}):
         print(f"  refused: {msg[:160]}")

@@ -206,3 +206,30 @@ def test_launch_trace_names():
         with ops.launch_trace(0) as tr:
             _new(c, t)
         assert tr.counts == {f"attn_prefix_partial_kernel<{m[2]}>": 1, name: 1}, tr.counts
+
+
+@pytest.mark.parametrize("d", (64, 128))
+def test_row_kernel_with_an_empty_prefix_is_attn_decode(d):
+    """attn_own_merge_row_kernel and attn_decode_kernel are one function (dec_stream + dec_group_merge, csrc/attn_decode_core.h): with the partial
+    px_attend documents for no keys (o = 0, m = -1e30, l = 0) in the workspace the merge is O / L, and the outputs must be bit-equal - at every key
+    count around the 16-key group and the 32-key prefetch edges, one row each through kv_start."""
+    keys = (1, 15, 16, 17, 31, 32, 33, 47, 48, 49, 65, 97)
+    H, B, Tmax, ctx = 2, len(keys), 104, 97
+    g = torch.Generator().manual_seed(d)
+    q = torch.randn((B, H * d), generator=g).to(BF16).to(DEV)
+    kc = torch.full((B, H, Tmax, d), float("nan"), dtype=BF16); vc = kc.clone()
+    for b, n in enumerate(keys):
+        kc[b, :, ctx - n:ctx] = (0.5 * torch.randn((H, n, d), generator=g)).to(BF16)
+        vc[b, :, ctx - n:ctx] = torch.randn((H, n, d), generator=g).to(BF16)
+    kc, vc = kc.to(DEV), vc.to(DEV)
+    kv_start = torch.tensor([ctx - n for n in keys], dtype=torch.int32, device=DEV)
+    part = torch.zeros((B * H, d + 2), dtype=torch.float32, device=DEV)
+    part[:, d] = -1e30
+    ws = part.view(torch.uint8).reshape(-1)
+    assert ws.numel() == ops.attn_prefix_bytes(B, H, d)
+    with ops.launch_trace(0) as tr:
+        got = ops.attn_own_merge(q, ws, kc, vc, torch.zeros_like(q), B, 1, H, H, d, Tmax, ctx, d ** -0.5, kv_start=kv_start)
+        ref = ops.attn_decode(q, kc, vc, torch.zeros_like(q), B, H, H, d, Tmax, ctx, d ** -0.5, kv_start=kv_start)
+    assert tr.counts == {f"attn_own_merge_row_kernel<{d}>": 1, f"attn_decode_kernel<{d}>": 1}, tr.counts
+    assert torch.isfinite(ref.float()).all()
+    assert torch.equal(got, ref), (got.float() - ref.float()).abs().max().item()
