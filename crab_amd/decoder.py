@@ -1026,7 +1026,19 @@ class GenerationEngine:
     def _select(self, st: "_DecodeState"):
         """Next token of every row from st.logits: greedy (argmax) or, with st.sampling = (temperature, top_k, top_p, seed), HF's sample
         mode (temperature -> top-k -> top-p -> draw) - both device-resident, so the step stays capturable.  A state with a token trie (st.trie:
-        closed-set generation) takes both among the out-edges of every row's node instead (ops.constrained_select; st.node follows the edge)."""
+        closed-set generation) takes both among the out-edges of every row's node instead (ops.constrained_select; st.node follows the edge).
+        A state with st.lp (return_logprobs) also records the log-probability of the chosen token: the normalisers of the raw logits are taken
+        BEFORE the select (it sets `finished` and moves st.node), the token's logit is gathered AFTER it (ops.logprob_norm / logprob_gather); the
+        select itself is the same launch either way."""
+        if st.lp is not None:
+            tr = st.trie
+            ops.logprob_norm(st.logits, st.step_dev, st.finished, st.eos, st.min_new, st.lp_norm, tr.edge_off if tr is not None else None,
+                             tr.edge_tok if tr is not None else None, st.node)
+        self._select_token(st)
+        if st.lp is not None:
+            ops.logprob_gather(st.logits, st.cur_ids, st.step_dev, st.lp_norm, st.lp)
+
+    def _select_token(self, st: "_DecodeState"):
         if st.trie is not None:
             t, k, p_, seed = st.sampling if st.sampling is not None else (0.0, 0, 1.0, 0)
             ops.constrained_select(st.logits, st.trie.edge_off, st.trie.edge_tok, st.trie.edge_dst, st.node, st.cur_ids, st.out_ids, st.step_dev,
@@ -1038,14 +1050,16 @@ class GenerationEngine:
             ops.sample_select(st.logits, st.cur_ids, st.out_ids, st.step_dev, st.finished, st.eos, st.pad, st.min_new, t, k, p_, seed + 7919 * st.slot)
 
     def _state(self, B: int, S: int, max_new_tokens: int, eos_token_id, pad_token_id, min_new_tokens: int, return_hidden: bool, slot: int,
-               sampling=None, ragged: bool = False, extra_key=(), constraint=None) -> "_DecodeState":
+               sampling=None, ragged: bool = False, extra_key=(), constraint=None, logprobs: bool = False) -> "_DecodeState":
         """The persistent decode state of `slot` for B sequences whose (longest) prompt has S rows: KV cache, per-row words, logits and the HIP
         graph captured over them.  Kept per slot and reused by every call whose shapes, flags and buffers are the same: the key holds
         everything the captured launches bake in (pointers included).  ragged: the state of a coalesced batch (generate_many(coalesce=True)) -
         it owns a row_off word per row (first cache slot of the row's sequence) that the captured decode step reads.  extra_key: what else a caller's captured step bakes in
         (generate_shared_prefix: the prefix cache, its length, the tile plan and the workspace).  constraint: the rows' _Constraint (closed-set
         generation) - the trie's device pointers enter the key, so a captured graph never crosses tries, and every call puts the rows back on
-        their roots."""
+        their roots.  logprobs: the state owns st.lp [2, B, max_new_tokens] fp32 (plane 0: log-probability of every emitted token over the
+        whole vocabulary, plane 1: within the allowed set; zeroed by every call like out_ids) and st.lp_norm [B, 4], and _select fills them;
+        the flag is part of the key, so a graph captured without the two launches is never replayed for a call that wants them."""
         if int(max_new_tokens) < 1:                             # HF: GenerationConfig.validate() - "`max_new_tokens` must be greater than 0"; here the first token's slot would not exist
             raise ValueError(f"`max_new_tokens` must be greater than 0, but is {max_new_tokens}.")
         dev = self.device
@@ -1072,7 +1086,7 @@ class GenerationEngine:
                tab.data_ptr(), self.lm_head.weight.data_ptr(), self.model.embed_tokens.weight.data_ptr(),
                self.model.layers[0].self_attn._qkv.W.data_ptr(),
                self.model.layers[0].self_attn._qkv.RA is not None, sampling, bool(ragged),
-               self._kv_mode, ks.data_ptr() if ks is not None else 0, vs.data_ptr() if vs is not None else 0, w8_key) + tuple(extra_key) + \
+               self._kv_mode, ks.data_ptr() if ks is not None else 0, vs.data_ptr() if vs is not None else 0, w8_key, bool(logprobs)) + tuple(extra_key) + \
             (constraint.dev.key if constraint is not None else ())
         st = self._dec.get(slot)
         if st is None or st.key != key:
@@ -1094,10 +1108,14 @@ class GenerationEngine:
             st.prefix = None
             st.trie = constraint.dev if constraint is not None else None
             st.node = torch.empty((B,), device=dev, dtype=torch.int32) if constraint is not None else None
+            st.lp = torch.empty((2, B, max_new_tokens), device=dev, dtype=torch.float32) if logprobs else None
+            st.lp_norm = torch.zeros((B, 4), device=dev, dtype=torch.float32) if logprobs else None
             self._dec[slot] = st
         st.S = S
         st.cur_ids.zero_(); st.out_ids.fill_(pad_token_id if pad_token_id is not None else 0); st.finished.zero_()
         st.pos_dev.fill_(S - 1); st.step_dev.zero_()
+        if st.lp is not None:
+            st.lp.zero_()
         if constraint is not None:
             assert len(constraint.roots) == B, "one trie root per row"
             st.node.copy_(torch.tensor(constraint.roots, dtype=torch.int32))
@@ -1118,10 +1136,11 @@ class GenerationEngine:
         ops.kv_quant_fp8(sk, sv, st.kc, st.vc, st.ks, st.vs, b0=b0, t0=0, t_dst=t0, S=S, row_off=kv_start)
 
     def _start(self, embeds: torch.Tensor, max_new_tokens: int, eos_token_id, pad_token_id, min_new_tokens: int, prefill_chunk: int,
-               return_hidden: bool, slot: int, sink=None, sampling=None, constraint=None) -> "_DecodeState":
+               return_hidden: bool, slot: int, sink=None, sampling=None, constraint=None, logprobs: bool = False) -> "_DecodeState":
         """Allocate the decode state of one group of sequences, prefill it and select its first token."""
         B, S, D = embeds.shape
-        st = self._state(B, S, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, return_hidden, slot, sampling, constraint=constraint)
+        st = self._state(B, S, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, return_hidden, slot, sampling, constraint=constraint,
+                         logprobs=logprobs)
         # ---- prefill in chunks of sequences (bounds activation memory, keeps GEMM M in the MFMA-efficient range)
         chunks = self.plan_prefill_chunks(B, S) if not prefill_chunk else [prefill_chunk] * (B // prefill_chunk) + \
             ([B % prefill_chunk] if B % prefill_chunk else [])
@@ -1167,7 +1186,7 @@ class GenerationEngine:
             g = g1 + 1
 
     def _start_ragged(self, embeds_list: List[torch.Tensor], max_new_tokens: int, eos_token_id, pad_token_id, min_new_tokens: int,
-                      sink=None, sampling=None, return_hidden: bool = False, constraint=None) -> "_DecodeState":
+                      sink=None, sampling=None, return_hidden: bool = False, constraint=None, logprobs: bool = False) -> "_DecodeState":
         """The decode state of SEVERAL generate() calls coalesced into one batch.  Group g = [B_g, S_g, D] is one call of the eval loop: its
         own prompt length and left padding, positions 0 .. S_g - 1 (unified_llama.py:262-267).  All rows share one KV cache [L, sum B_g, Hk,
         Tmax, d] in which every group is RIGHT-ALIGNED at Smax = max S_g: group g's prompt occupies slots Smax - S_g .. Smax - 1, so the token
@@ -1180,7 +1199,7 @@ class GenerationEngine:
         Ss = [int(e.shape[1]) for e in embeds_list]
         Bt, Smax = sum(Bs), max(Ss)
         st = self._state(Bt, Smax, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, return_hidden, 0, sampling, ragged=True,
-                         constraint=constraint)
+                         constraint=constraint, logprobs=logprobs)
         st.row_off.copy_(torch.tensor([Smax - S for B, S in zip(Bs, Ss) for _ in range(B)], dtype=torch.int32), non_blocking=False)
         waste = sum(B * (Smax - S) for B, S in zip(Bs, Ss)) / max(1, sum(B * S for B, S in zip(Bs, Ss)))
         if len(set(Ss)) > 1 and waste <= RAGGED_PAD_MAX:
@@ -1231,15 +1250,22 @@ class GenerationEngine:
                  pad_token_id: Optional[int] = None, min_new_tokens: int = 0, prefill_chunk: int = 0, use_graph: bool = True,
                  return_step_logits: bool = False, return_hidden: bool = False, decode_streams: int = 1,
                  return_first_logits: bool = False, sampling=None, kv_cache_dtype: Optional[str] = None, weight_dtype: Optional[str] = None,
-                 constraint=None):
+                 constraint=None, return_logprobs: bool = False):
         """kv_cache_dtype / weight_dtype: "bf16" / "fp8_e4m3" for this call (None: the engine's); see _generate for the rest.
         constraint = (TokenTrie, one set index per row or None): closed-set generation (crab_amd/constrain.py) - every row's ids, cut at EOS,
         are a member of the row's answer set; greedy and sample mode both choose among the trie's edges on the device, everything else (KV and
         weight modes, EOS trim, padding of finished rows) is unchanged.  A row that max_new_tokens cuts in the middle of an answer holds a
-        proper prefix of a member, as HF's constrained decode does."""
+        proper prefix of a member, as HF's constrained decode does.
+        return_logprobs: the result gains, as its LAST element, an fp32 tensor [B, n, 2] beside the ids [B, n]: [..., 0] the log-probability of every
+        emitted token over the whole vocabulary (raw logits: no EOS suppression, no temperature, no trie - the number score() gives teacher-forced
+        on the same ids), [..., 1] the same within the set the step chose from (all but EOS while min_new_tokens holds; the trie's edges in a
+        constrained call) - HF's compute_transition_scores(normalize_logits=True) of a greedy call.  0.0 where the row emitted no token
+        (padding after its EOS; the EOS column itself is a token).  Sample mode: the warpers are a drawing device and enter neither number
+        (HF's warped `scores` are not reproduced).  Written inside the decode step (csrc/logprob.hip): no host sync, nothing of size B x V kept."""
         cons, = self._constraints(constraint, [int(embeds.shape[0])], eos_token_id, min_new_tokens, flat=True)
         return self._call(kv_cache_dtype, weight_dtype, self._generate, embeds, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens,
-                          prefill_chunk, use_graph, return_step_logits, return_hidden, decode_streams, return_first_logits, sampling, cons)
+                          prefill_chunk, use_graph, return_step_logits, return_hidden, decode_streams, return_first_logits, sampling, cons,
+                          return_logprobs)
 
     def _run_steps(self, sts: List["_DecodeState"], max_new_tokens: int, graphed: bool, side_streams: bool, retire: bool, on_step=None,
                    sampled_step=None):
@@ -1293,7 +1319,7 @@ class GenerationEngine:
     def _generate(self, embeds: torch.Tensor, max_new_tokens: int, eos_token_id: Optional[int] = None,
                   pad_token_id: Optional[int] = None, min_new_tokens: int = 0, prefill_chunk: int = 0, use_graph: bool = True,
                   return_step_logits: bool = False, return_hidden: bool = False, decode_streams: int = 1,
-                  return_first_logits: bool = False, sampling=None, constraint=None):
+                  return_first_logits: bool = False, sampling=None, constraint=None, return_logprobs: bool = False):
         """Greedy generation from inputs_embeds only, as UnifiedForCausalLM.generate drives HF generate
         (unified_llama.py:262-267): positions 0..S-1 (left pads attended), returns ONLY new ids.
 
@@ -1310,7 +1336,7 @@ class GenerationEngine:
         groups = self.plan_batch(B, S, max_new_tokens, slots=max(1, decode_streams))
         if len(groups) > 1:
             return self._generate_split(groups, embeds, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, prefill_chunk, use_graph,
-                                        return_step_logits, return_hidden, return_first_logits, sampling, constraint)
+                                        return_step_logits, return_hidden, return_first_logits, sampling, constraint, return_logprobs)
         graphed = use_graph and max_new_tokens > 2
         G = decode_streams if (decode_streams > 1 and graphed and B >= decode_streams and
                                not return_step_logits and not return_hidden) else 1
@@ -1340,7 +1366,7 @@ class GenerationEngine:
             with _ws_slot(g):
                 sts.append(self._start(embeds[B * g // G:B * (g + 1) // G], max_new_tokens, eos_token_id, pad_token_id, min_new_tokens,
                                        prefill_chunk, return_hidden, g, sink, sampling,
-                                       constraint.rows(B * g // G, B * (g + 1) // G) if constraint is not None else None))
+                                       constraint.rows(B * g // G, B * (g + 1) // G) if constraint is not None else None, return_logprobs))
         if ops.PROFILER is not None:
             ops.PROFILER.mark("prefill_end")
         # the groups are ONE call: all of them step until all have finished (a retired group's buffer would hold the fill value, not its pad id)
@@ -1358,6 +1384,8 @@ class GenerationEngine:
             res.append(torch.stack(hiddens, 1)[:, : out.shape[1]])
         if return_first_logits:
             res.append(first_logits[0] if G == 1 else torch.cat(first_logits, 0))
+        if return_logprobs:
+            res.append(torch.cat([_lp_rows(st, 0, st.B, out.shape[1]) for st in sts], 0))
         return res[0] if len(res) == 1 else tuple(res)
 
     @torch.no_grad()
@@ -1365,18 +1393,21 @@ class GenerationEngine:
                       pad_token_id: Optional[int] = None, min_new_tokens: int = 0, use_graph: bool = True, sampling=None,
                       return_first_logits: bool = False, coalesce: bool = False, max_rows: Optional[int] = None,
                       return_step_logits: bool = False, return_hidden: bool = False, kv_cache_dtype: Optional[str] = None,
-                      weight_dtype: Optional[str] = None, constraint=None):
+                      weight_dtype: Optional[str] = None, constraint=None, return_logprobs: bool = False):
         """kv_cache_dtype / weight_dtype: "bf16" / "fp8_e4m3" for this call (None: the engine's); see _generate_many for the rest.
+        return_logprobs: every batch's result gains a LAST element, fp32 [B_g, n_g, 2], as in generate(); a row's scores follow the row into the
+        in-flight states and the ragged waves.
         constraint = (TokenTrie, one list of set indices per batch or None): closed-set generation as in generate(); the set indices follow
         their rows into the in-flight states and the ragged waves."""
         cons = self._constraints(constraint, [int(e.shape[0]) for e in embeds_list], eos_token_id, min_new_tokens) if constraint is not None else None
         return self._call(kv_cache_dtype, weight_dtype, self._generate_many, embeds_list, max_new_tokens, eos_token_id, pad_token_id,
-                          min_new_tokens, use_graph, sampling, return_first_logits, coalesce, max_rows, return_step_logits, return_hidden, cons)
+                          min_new_tokens, use_graph, sampling, return_first_logits, coalesce, max_rows, return_step_logits, return_hidden, cons,
+                          return_logprobs)
 
     def _generate_many(self, embeds_list: List[torch.Tensor], max_new_tokens: int, eos_token_id: Optional[int] = None,
                        pad_token_id: Optional[int] = None, min_new_tokens: int = 0, use_graph: bool = True, sampling=None,
                        return_first_logits: bool = False, coalesce: bool = False, max_rows: Optional[int] = None,
-                       return_step_logits: bool = False, return_hidden: bool = False, constraints=None):
+                       return_step_logits: bool = False, return_hidden: bool = False, constraints=None, return_logprobs: bool = False):
         """Several INDEPENDENT batches in flight: each element of `embeds_list` ([B_i, S_i, D], its own prompt length and left padding, i.e.
         exactly what one generate() call of the reference's eval loop gets) becomes one decode group with its own KV cache, decode state
         and captured HIP graph; the groups are prefilled one after the other and their decode steps are replayed on separate HIP streams.
@@ -1405,10 +1436,11 @@ class GenerationEngine:
             raise NotImplementedError("generate_many: return_step_logits / return_hidden are options of the coalesced form, one at a time (use generate() per batch otherwise)")
         if coalesce and (G > 1 or return_step_logits or return_hidden):
             return self._generate_coalesced(embeds_list, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling,
-                                            return_first_logits, max_rows, return_step_logits, return_hidden, cons)
+                                            return_first_logits, max_rows, return_step_logits, return_hidden, cons, return_logprobs)
         if G == 1:
             return [self._generate(embeds_list[0], max_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id, min_new_tokens=min_new_tokens,
-                                   use_graph=use_graph, sampling=sampling, return_first_logits=return_first_logits, constraint=cons[0])]
+                                   use_graph=use_graph, sampling=sampling, return_first_logits=return_first_logits, constraint=cons[0],
+                                   return_logprobs=return_logprobs)]
         need = sum(e.shape[0] * self.bytes_per_sequence(e.shape[1], max_new_tokens) for e in embeds_list) + self.fixed_bytes(max(e.shape[0] for e in embeds_list),
                                                                                                                             max(e.shape[1] for e in embeds_list))
         budget = self.memory_budget(0, 0, slots=G)
@@ -1424,16 +1456,20 @@ class GenerationEngine:
         sts = []
         for g, emb in enumerate(embeds_list):
             with _ws_slot(g):
-                sts.append(self._start(emb, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, 0, False, g, sink, sampling, cons[g]))
+                sts.append(self._start(emb, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, 0, False, g, sink, sampling, cons[g],
+                                       return_logprobs))
         self._run_steps(sts, max_new_tokens, use_graph and max_new_tokens > 2, True, True)
         outs = []
         for g, st in enumerate(sts):
             out = _trim_at_eos(st.out_ids, int(st.step_dev.item()), st.eos).clone()
-            outs.append((out, firsts[g]) if return_first_logits else out)
+            r = (out, firsts[g]) if return_first_logits else (out,)
+            if return_logprobs:
+                r += (_lp_rows(st, 0, st.B, out.shape[1]),)
+            outs.append(r if len(r) > 1 else out)
         return outs
 
     def _generate_coalesced(self, embeds_list, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling,
-                            return_first_logits, max_rows, return_step_logits=False, return_hidden=False, cons=None):
+                            return_first_logits, max_rows, return_step_logits=False, return_hidden=False, cons=None, return_logprobs=False):
         """generate_many(coalesce=True): pack the batches, in order, into waves of at most `cap` rows (the weight-streaming regime of the decode
         projections, and what the device's memory holds at the longest prompt), run every wave as one ragged batch."""
         Bs = [int(e.shape[0]) for e in embeds_list]
@@ -1451,19 +1487,20 @@ class GenerationEngine:
                 g = w[0]
                 outs[g] = self._generate(embeds_list[g], max_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
                                          min_new_tokens=min_new_tokens, use_graph=use_graph, sampling=sampling, return_first_logits=return_first_logits,
-                                         return_step_logits=return_step_logits, return_hidden=return_hidden, constraint=cons[g])
+                                         return_step_logits=return_step_logits, return_hidden=return_hidden, constraint=cons[g],
+                                         return_logprobs=return_logprobs)
                 continue
             # the rows of the wave are the rows of its batches in wave order: so are their trie roots
             wc = _Constraint(cons[w[0]].dev, [r for g in w for r in cons[g].roots]) if cons[w[0]] is not None else None
             res = self._ragged_wave([embeds_list[g] for g in w], max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling,
-                                    return_first_logits, return_step_logits, return_hidden, wc)
+                                    return_first_logits, return_step_logits, return_hidden, wc, return_logprobs)
             for g, r in zip(w, res):
                 outs[g] = r
         self.last_plan = plan
         return outs
 
     def _ragged_wave(self, embeds_list, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling, return_first_logits,
-                     return_step_logits=False, return_hidden=False, constraint=None):
+                     return_step_logits=False, return_hidden=False, constraint=None, return_logprobs=False):
         firsts, steps = [], []
 
         def sink(st):
@@ -1475,7 +1512,8 @@ class GenerationEngine:
                 steps.append(st.hn.clone())
 
         with _ws_slot(0):
-            st = self._start_ragged(embeds_list, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, sink, sampling, return_hidden, constraint)
+            st = self._start_ragged(embeds_list, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, sink, sampling, return_hidden, constraint,
+                                    return_logprobs)
         if ops.PROFILER is not None:
             ops.PROFILER.mark("prefill_end")
         self._run_steps([st], max_new_tokens, use_graph and max_new_tokens > 2, False, True,
@@ -1490,9 +1528,12 @@ class GenerationEngine:
             # what this batch's own generate() call returns: HF stops a call as soon as all of ITS rows have finished
             out = _trim_at_eos(st.out_ids[r0:r1], n_done, st.eos).clone()
             if return_step_logits or return_hidden:
-                outs.append((out, sl[r0:r1, : out.shape[1]].clone()))
+                r = (out, sl[r0:r1, : out.shape[1]].clone())
             else:
-                outs.append((out, firsts[0][r0:r1].clone()) if return_first_logits else out)
+                r = (out, firsts[0][r0:r1].clone()) if return_first_logits else (out,)
+            if return_logprobs:
+                r += (_lp_rows(st, r0, r1, out.shape[1]),)
+            outs.append(r if len(r) > 1 else out)
             r0 = r1
         return outs
 
@@ -1561,7 +1602,7 @@ class GenerationEngine:
     def generate_shared_prefix(self, prefix_embeds: torch.Tensor, suffix_embeds, max_new_tokens: int, eos_token_id: Optional[int] = None,
                                pad_token_id: Optional[int] = None, min_new_tokens: int = 0, use_graph: bool = True, sampling=None,
                                return_first_logits: bool = False, return_step_logits: bool = False, kv_cache_dtype: Optional[str] = None,
-                               weight_dtype: Optional[str] = None, max_rows: Optional[int] = None, constraint=None):
+                               weight_dtype: Optional[str] = None, max_rows: Optional[int] = None, constraint=None, return_logprobs: bool = False):
         """Several questions per clip on ONE prefix KV.  prefix_embeds [C, P, D] bf16: the shared part of C clips (everything up to the question
         text; the same P for all).  suffix_embeds: C lists, one [S_cg, D] tensor per question of the clip.  Returns one id tensor per clip,
         [G_c, n] (with return_first_logits (ids, fp32 [G_c, V]); with return_step_logits (ids, fp32 [G_c, n, V])): what
@@ -1578,13 +1619,14 @@ class GenerationEngine:
         More rows than a decode step takes (ops.DECODE_MAX_ROWS, max_rows) or than fit the memory run as consecutive waves of whole clips
         (plan_shared_prefix).  Sample mode draws per (seed, step, row of the wave), as the coalesced form does.
         kv_cache_dtype = "fp8_e4m3" and weight_dtype = "fp8_e4m3" raise NotImplementedError: the shared prefix is a bf16 path.
-        constraint = (TokenTrie, one list per clip with one set index per question, or None): closed-set generation as in generate()."""
+        constraint = (TokenTrie, one list per clip with one set index per question, or None): closed-set generation as in generate().
+        return_logprobs: every clip's result gains a LAST element, fp32 [G_c, n, 2], as in generate()."""
         cons = self._constraints(constraint, [len(qs) for qs in suffix_embeds], eos_token_id, min_new_tokens) if constraint is not None else None
         return self._call(kv_cache_dtype, weight_dtype, self._generate_shared_prefix, prefix_embeds, suffix_embeds, max_new_tokens, eos_token_id,
-                          pad_token_id, min_new_tokens, use_graph, sampling, return_first_logits, return_step_logits, max_rows, cons)
+                          pad_token_id, min_new_tokens, use_graph, sampling, return_first_logits, return_step_logits, max_rows, cons, return_logprobs)
 
     def _generate_shared_prefix(self, prefix_embeds, suffix_embeds, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling,
-                                return_first_logits, return_step_logits, max_rows, cons=None):
+                                return_first_logits, return_step_logits, max_rows, cons=None, return_logprobs=False):
         if self._fp8:
             raise NotImplementedError('kv_cache_dtype="fp8_e4m3" with a shared prefix (generate_shared_prefix) is not implemented: the prefix cache and its attention kernels are bf16')
         if getattr(self, "_w_mode", "bf16") == "fp8_e4m3":
@@ -1603,11 +1645,11 @@ class GenerationEngine:
         for w in self.plan_shared_prefix(Gs, P, Smax, max_new_tokens, max_rows):
             wc = _Constraint(cons[w[0]].dev, [r for c in w for r in cons[c].roots]) if cons is not None else None      # one root per question, in row order
             outs += self._shared_prefix_wave(prefix_embeds[w[0]:w[-1] + 1], [suffix_embeds[c] for c in w], max_new_tokens, eos_token_id, pad_token_id,
-                                             min_new_tokens, use_graph, sampling, return_first_logits, return_step_logits, wc)
+                                             min_new_tokens, use_graph, sampling, return_first_logits, return_step_logits, wc, return_logprobs)
         return outs
 
     def _shared_prefix_wave(self, prefix_embeds, suffix_embeds, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling,
-                            return_first_logits, return_step_logits, constraint=None):
+                            return_first_logits, return_step_logits, constraint=None, return_logprobs=False):
         C, P, D = prefix_embeds.shape
         Gs = [len(qs) for qs in suffix_embeds]
         flat = [q for qs in suffix_embeds for q in qs]
@@ -1632,7 +1674,7 @@ class GenerationEngine:
                 self.prefill(prefix_embeds[b0:b0 + n], px.decode.pk, px.decode.pv, b0=b0, want_logits=False)
                 b0 += n
             st = self._state(B, Smax, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, False, 0, sampling, ragged=True, extra_key=px.key,
-                             constraint=constraint)
+                             constraint=constraint, logprobs=return_logprobs)
             st.prefix = px.decode
             st.row_off.copy_(torch.tensor(lay["first_slot"], dtype=torch.int32))
             px.decode.rope_off.copy_(torch.tensor(lay["rope_off"], dtype=torch.int32))
@@ -1660,14 +1702,17 @@ class GenerationEngine:
             r1 = r0 + G
             out = _trim_at_eos(st.out_ids[r0:r1], n_done, st.eos).clone()
             if return_step_logits:
-                outs.append((out, sl[r0:r1, : out.shape[1]].clone()))
+                r = (out, sl[r0:r1, : out.shape[1]].clone())
             else:
-                outs.append((out, firsts[0][r0:r1].clone()) if return_first_logits else out)
+                r = (out, firsts[0][r0:r1].clone()) if return_first_logits else (out,)
+            if return_logprobs:
+                r += (_lp_rows(st, r0, r1, out.shape[1]),)
+            outs.append(r if len(r) > 1 else out)
             r0 = r1
         return outs
 
     def _generate_split(self, groups, embeds, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, prefill_chunk, use_graph,
-                        return_step_logits, return_hidden, return_first_logits, sampling=None, constraint=None):
+                        return_step_logits, return_hidden, return_first_logits, sampling=None, constraint=None, return_logprobs=False):
         """The batch does not fit the device's memory in one piece: generate the groups one after the other (rows are independent,
         so the results are those of the one-piece run up to the kernel choice a different M implies) and join them.  A group
         that finished early (EOS) is padded to the longest group's length with pad ids, like HF pads finished rows."""
@@ -1685,7 +1730,7 @@ class GenerationEngine:
                                    min_new_tokens=min_new_tokens, prefill_chunk=prefill_chunk, use_graph=use_graph,
                                    return_step_logits=return_step_logits, return_hidden=return_hidden, return_first_logits=return_first_logits,
                                    sampling=None if sampling is None else (sampling[0], sampling[1], sampling[2], sampling[3] + 104729 * b0),
-                                   constraint=constraint.rows(b0, b0 + n) if constraint is not None else None)
+                                   constraint=constraint.rows(b0, b0 + n) if constraint is not None else None, return_logprobs=return_logprobs)
             finally:
                 self.kv_budget_bytes = saved
             parts.append(r if isinstance(r, tuple) else (r,))
@@ -1697,7 +1742,7 @@ class GenerationEngine:
             cols = []
             for q in parts:
                 t = q[j]
-                per_step = t.dim() >= 2 and not (return_first_logits and j == len(parts[0]) - 1)
+                per_step = t.dim() >= 2 and not (return_first_logits and j == len(parts[0]) - 1 - int(return_logprobs))      # the scores come last
                 if per_step and t.shape[1] < n_max:
                     fill = torch.full((t.shape[0], n_max - t.shape[1]) + tuple(t.shape[2:]), pad if j == 0 else 0, device=t.device, dtype=t.dtype)
                     t = torch.cat([t, fill], 1)
@@ -1734,6 +1779,12 @@ class GenerationEngine:
 
 class _DecodeState:
     pass
+
+
+def _lp_rows(st: "_DecodeState", r0: int, r1: int, n: int) -> torch.Tensor:
+    """The scores of rows r0 .. r1 of a state for the n columns its ids were trimmed to, as a fresh [r1 - r0, n, 2] tensor (st.lp is the
+    persistent, graph-baked buffer the next call refills)."""
+    return st.lp[:, r0:r1, :n].permute(1, 2, 0).contiguous()
 
 
 class _Constraint:

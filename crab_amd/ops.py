@@ -695,6 +695,55 @@ def constrained_select(logits, edge_off, edge_tok, edge_dst, node, cur_ids, out_
                                                    int(seed) & 0xFFFFFFFFFFFFFFFF), d)
 
 
+def _chk_f32(name: str, t: torch.Tensor, shape, device):
+    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or t.device != device:
+        raise ValueError(f"{name} must be a float32 {list(shape)} tensor on {device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+
+
+def logprob_norm(logits, step_dev, finished, eos_id: int, min_new_tokens: int, norm, edge_off=None, edge_tok=None, node=None):
+    """crab_logprob_norm (csrc/logprob.hip), BEFORE the select of a decode step: norm[b] = (logsumexp of the raw row, logsumexp over the tokens the
+    select may choose - all but EOS while step < min_new_tokens, or the out-edges of node[b] with a trie -, live, 0).  logits [B, V] fp32 (any row
+    stride), norm fp32 [B, 4]; the trie arrays as constrained_select takes them, all three or none."""
+    d = _dev(logits)
+    B, V = logits.shape
+    if logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise ValueError(f"logits must be float32 rows with unit column stride, got {logits.dtype} strides {logits.stride()}")
+    _chk_f32("norm", norm, (B, 4), logits.device)
+    if not norm.is_contiguous():
+        raise ValueError("norm must be contiguous")
+    _chk_i32("finished", finished, B, logits.device)
+    _chk_i32("step_dev", step_dev, 1, logits.device)
+    n_nodes = n_edges = 0
+    if edge_off is not None or edge_tok is not None or node is not None:
+        if edge_off is None or edge_tok is None or node is None:
+            raise ValueError("edge_off, edge_tok and node come together")
+        n_nodes, n_edges = int(edge_off.shape[0]) - 1, int(edge_tok.shape[0])
+        _chk_i32("edge_off", edge_off, n_nodes + 1, logits.device)
+        _chk_i32("edge_tok", edge_tok, n_edges, logits.device)
+        _chk_i32("node", node, B, logits.device)
+    _lib.check(_lib.load().crab_logprob_norm(_lib.ctx(d), _stream(), _p(logits), logits.stride(0), B, V, _p(edge_off), _p(edge_tok), n_nodes, n_edges,
+                                             _p(node), _p(step_dev), _p(finished), eos_id, min_new_tokens, _p(norm)), d)
+
+
+def logprob_gather(logits, cur_ids, step_dev, norm, lp):
+    """crab_logprob_gather, AFTER the select and before advance: lp[0, b, step] = z[y] - norm[b, 0], lp[1, b, step] = z[y] - norm[b, 1] with
+    y = cur_ids[b], step = step_dev[0]; both 0 for a row that was not live (norm[b, 2] == 0) or a token outside [0, V); nothing when step is
+    past lp's last column.  lp fp32 [2, B, n_steps] with unit column stride."""
+    d = _dev(logits)
+    B, V = logits.shape
+    if logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise ValueError(f"logits must be float32 rows with unit column stride, got {logits.dtype} strides {logits.stride()}")
+    _chk_f32("norm", norm, (B, 4), logits.device)
+    if lp.dtype != torch.float32 or lp.dim() != 3 or lp.shape[0] != 2 or lp.shape[1] != B or lp.shape[2] < 1 or lp.stride(2) != 1 or \
+            lp.stride(1) < lp.shape[2] or lp.stride(0) < 0 or lp.device != logits.device or not norm.is_contiguous():
+        raise ValueError(f"lp must be a float32 [2, {B}, n_steps] tensor with unit column stride on {logits.device}, got {lp.dtype} {tuple(lp.shape)}")
+    if cur_ids.dtype != torch.int64 or cur_ids.shape[0] < B or not cur_ids.is_contiguous():
+        raise ValueError(f"cur_ids must be a contiguous int64 [{B}] tensor, got {cur_ids.dtype} {tuple(cur_ids.shape)}")
+    _chk_i32("step_dev", step_dev, 1, logits.device)
+    _lib.check(_lib.load().crab_logprob_gather(_lib.ctx(d), _stream(), _p(logits), logits.stride(0), B, V, _p(cur_ids), _p(step_dev), _p(norm),
+                                               _p(lp), lp.stride(1), lp.stride(0), int(lp.shape[2])), d)
+
+
 def advance(pos_dev, step_dev):
     d = _dev(pos_dev)
     _lib.check(_lib.load().crab_advance(_lib.ctx(d), _stream(), _p(pos_dev), _p(step_dev)), d)

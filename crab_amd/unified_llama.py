@@ -277,7 +277,14 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
         callback between two tokens and stays refused).  allowed_sequences: a TokenTrie, one list of id sequences (one answer set for every row)
         or a list of such lists (several sets); allowed_set: one set index per row (default set 0; required with several sets).  Every row's
         ids, cut at EOS, are then a member of its set - greedy and do_sample alike; needs one eos_token_id, and min_new_tokens at most the
-        shortest member.  A row that max_new_tokens cuts in the middle of an answer holds a proper prefix of a member, as in HF."""
+        shortest member.  A row that max_new_tokens cuts in the middle of an answer holds a proper prefix of a member, as in HF.
+        output_token_logprobs (not an HF name; what replaces output_scores + compute_transition_scores): the result is a
+        GenerateOutput with .sequences [B, n] and, all fp32 but the last, .token_logprobs [B, n] (log-probability of every generated token over
+        the whole vocabulary, from the raw logits - the number score() gives teacher-forced), .token_logprobs_allowed [B, n] (the same within
+        the set the step chose from: all but EOS under min_new_tokens, the answer trie's edges in a closed-set call = HF's transition scores
+        with normalize_logits=True of a greedy call), .sum_logprob [B], .sum_logprob_allowed [B] and .num_tokens [B] (int32: generated tokens, the
+        EOS included).  Entries after a row's EOS are 0.  With do_sample the warpers (temperature, top_k, top_p) enter neither number - they
+        describe the model, not the draw; HF's warped `scores` are not reproduced."""
         self._check_generate_kwargs(kwargs)
         sampling = self._sampling(kwargs)
         constraint = self._constraint(kwargs)
@@ -295,15 +302,18 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
         pad = kwargs.get("pad_token_id", self.model.pad_token_id if self.model.pad_token_id is not None else eos)
         want_logits = bool(kwargs.get("output_logits")) and bool(kwargs.get("return_dict_in_generate"))
         want_first = bool(kwargs.get("output_first_logits"))      # not an HF name: ids + the first step's logits only (eval gather)
+        want_lp = bool(kwargs.get("output_token_logprobs"))       # not an HF name either: the chosen tokens' log-probabilities (csrc/logprob.hip)
         res = self._engine.generate(embeds, max_new, eos_token_id=eos, pad_token_id=pad,
                                     min_new_tokens=int(kwargs.get("min_new_tokens", 0) or 0),
                                     prefill_chunk=int(kwargs.get("prefill_chunk", 0)), use_graph=kwargs.get("use_graph", True),
                                     return_step_logits=want_logits, decode_streams=int(kwargs.get("decode_streams", 1)),
                                     return_first_logits=want_first, sampling=sampling, kv_cache_dtype=kwargs.get("kv_cache_dtype"), weight_dtype=kwargs.get("weight_dtype"),
-                                    constraint=constraint)
-        if want_logits or want_first:
+                                    constraint=constraint, return_logprobs=want_lp)
+        if want_logits or want_first or want_lp:
             res = list(res)
             out = type("GenerateOutput", (), {})()
+            if want_lp:
+                _fill_logprob_fields(out, res[0], res.pop(), eos)
             out.sequences = res.pop(0)
             if want_logits:
                 sl = res.pop(0)
@@ -324,7 +334,9 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
         stream once per step for all batches and the encoders run over the clips of all batches together, so batches of 8 reach the
         throughput of one large generate(); per-batch ids / logits agree with separate calls within the decoder's bf16 tolerance.
         Returns one id tensor per batch (with output_first_logits=True: (ids, fp32 logits of the first generated position)).
-        allowed_sequences / allowed_set: closed-set generation as in generate(); allowed_set is one list of set indices per batch."""
+        allowed_sequences / allowed_set: closed-set generation as in generate(); allowed_set is one list of set indices per batch.
+        output_token_logprobs=True: every batch's result is a GenerateOutput with the fields generate() gives it (.sequences, .token_logprobs,
+        .token_logprobs_allowed, .sum_logprob, .sum_logprob_allowed, .num_tokens; .first_logits with output_first_logits)."""
         for k in ("output_logits", "return_dict_in_generate", "inputs_embeds"):
             if kwargs.get(k) is not None and kwargs.get(k) is not False:
                 raise NotImplementedError(f"generate_batches returns token ids only: {k} is a generate() argument")
@@ -346,10 +358,13 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
                 embeds.append(inputs['inputs_embeds'].to(device=self.device, dtype=BF16))
         eos = kwargs.get("eos_token_id", self.config.eos_token_id)
         pad = kwargs.get("pad_token_id", self.model.pad_token_id if self.model.pad_token_id is not None else eos)
-        return self._engine.generate_many(embeds, int(kwargs.get("max_new_tokens", 20)), eos_token_id=eos, pad_token_id=pad,
-                                          min_new_tokens=int(kwargs.get("min_new_tokens", 0) or 0), use_graph=kwargs.get("use_graph", True),
-                                          sampling=sampling, return_first_logits=want_first, coalesce=coalesce, max_rows=max_rows,
-                                          kv_cache_dtype=kwargs.get("kv_cache_dtype"), weight_dtype=kwargs.get("weight_dtype"), constraint=constraint)
+        want_lp = bool(kwargs.get("output_token_logprobs"))
+        res = self._engine.generate_many(embeds, int(kwargs.get("max_new_tokens", 20)), eos_token_id=eos, pad_token_id=pad,
+                                         min_new_tokens=int(kwargs.get("min_new_tokens", 0) or 0), use_graph=kwargs.get("use_graph", True),
+                                         sampling=sampling, return_first_logits=want_first, coalesce=coalesce, max_rows=max_rows,
+                                         kv_cache_dtype=kwargs.get("kv_cache_dtype"), weight_dtype=kwargs.get("weight_dtype"), constraint=constraint,
+                                         return_logprobs=want_lp)
+        return [_logprob_output(r, want_first, eos) for r in res] if want_lp else res
 
     @torch.no_grad()
     def generate_questions(self, clips, max_rows: Optional[int] = None, **kwargs):
@@ -362,11 +377,13 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
         same length decode together (the engine takes one prefix length per call).  Returns one id tensor per clip, [questions, n]: row g is
         what generate() returns for the ids cat(shared, question g), within the decoder's bf16 tolerance (with output_first_logits=True:
         (ids, fp32 logits of the first generated position)).
-        allowed_sequences / allowed_set: closed-set generation as in generate(); allowed_set is one list per clip with one set index per question."""
+        allowed_sequences / allowed_set: closed-set generation as in generate(); allowed_set is one list per clip with one set index per question.
+        output_token_logprobs=True: every clip's result is a GenerateOutput as generate_batches returns it (one row per question)."""
         for k in ("output_logits", "return_dict_in_generate", "inputs_embeds"):
             if kwargs.get(k) is not None and kwargs.get(k) is not False:
                 raise NotImplementedError(f"generate_questions returns token ids only: {k} is a generate() argument")
         want_first = bool(kwargs.get("output_first_logits"))
+        want_lp = bool(kwargs.get("output_token_logprobs"))
         self._check_generate_kwargs(kwargs)
         sampling = self._sampling(kwargs)
         constraint = self._constraint(kwargs)
@@ -394,9 +411,10 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
                                                       sampling=sampling, return_first_logits=want_first, kv_cache_dtype=kwargs.get("kv_cache_dtype"),
                                                       weight_dtype=kwargs.get("weight_dtype"), max_rows=max_rows,
                                                       constraint=None if constraint is None else
-                                                      (constraint[0], None if constraint[1] is None else [constraint[1][i] for i in idx]))
+                                                      (constraint[0], None if constraint[1] is None else [constraint[1][i] for i in idx]),
+                                                      return_logprobs=want_lp)
             for i, r in zip(idx, res):
-                outs[i] = r
+                outs[i] = _logprob_output(r, want_first, eos) if want_lp else r
         return outs
 
     # HF generate() arguments that would CHANGE what is decoded and that this path does not implement: refused by name instead of ignored
@@ -544,3 +562,29 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
         r = super().load_state_dict(state_dict, strict=strict, assign=False)      # copy_ casts to each parameter's dtype
         self._invalidate_graphs()
         return r
+
+
+def _fill_logprob_fields(out, ids: torch.Tensor, lp: torch.Tensor, eos):
+    """The output_token_logprobs fields of a GenerateOutput from the engine's scores lp [B, n, 2] (GenerationEngine.generate(return_logprobs)):
+    names as in ScoreOutput.  num_tokens counts a row's ids up to and including its first EOS (all n without one)."""
+    out.token_logprobs, out.token_logprobs_allowed = lp[..., 0].contiguous(), lp[..., 1].contiguous()
+    out.sum_logprob, out.sum_logprob_allowed = out.token_logprobs.sum(1), out.token_logprobs_allowed.sum(1)
+    n = ids.shape[1]
+    if isinstance(eos, (list, tuple)):
+        eos = eos[0] if len(eos) else None
+    if eos is None or n == 0:
+        out.num_tokens = torch.full((ids.shape[0],), n, device=ids.device, dtype=torch.int32)
+    else:
+        hit = ids == int(eos)
+        first = torch.where(hit.any(1), hit.to(torch.int32).argmax(1) + 1, torch.full_like(ids[:, 0], n))
+        out.num_tokens = first.to(torch.int32)
+
+
+def _logprob_output(res, want_first: bool, eos):
+    """One batch / clip result of the engine with return_logprobs - (ids, [first logits,] scores) - as a GenerateOutput."""
+    out = type("GenerateOutput", (), {})()
+    out.sequences = res[0]
+    if want_first:
+        out.first_logits = res[1]
+    _fill_logprob_fields(out, res[0], res[-1], eos)
+    return out

@@ -434,6 +434,29 @@ int crab_constrained_select(crab_ctx* ctx, void* stream, const float* logits, in
                             const int32_t* edge_tok, const int32_t* edge_dst, int n_nodes, int n_edges, int32_t* node, int64_t* cur_ids,
                             int64_t* out_ids, int64_t ld_out, const int32_t* step_dev, int32_t* finished, int eos_id, int pad_id,
                             int min_new_tokens, float temperature, int top_k, float top_p, uint64_t seed);
+/* Per-token log-probabilities of the step (csrc/logprob.hip): what HF computes with output_scores = True + compute_transition_scores
+ * (normalize_logits = True), without keeping a [B, V] tensor per step and without a host read.  For row b with raw fp32 logits z = logits[b]
+ * and the token y the select chose:
+ *     logprob         = z[y] - logsumexp(z[0 .. V))                      (no suppression, no temperature, no trie: what scoring gives)
+ *     logprob_allowed = z[y] - logsumexp(z[i] : i allowed at this step)  allowed = what the select kernels choose from: every token but
+ *                       eos_id while step < min_new_tokens; with a trie the tokens of the out-edges of node[b] that lie in [0, V) and are not the
+ *                       suppressed EOS (crab_constrained_select's rule), node[b] as it stands BEFORE the select moves it.
+ * The sampling warpers (temperature, top_k, top_p) enter neither number.
+ * crab_logprob_norm runs BEFORE the select of the step: one block per row, one pass over the row (16-byte loads from the row's first 16-byte
+ * boundary on, scalar head / tail: any 4-byte aligned base and any ldl), writes norm[b] = (lse_raw, lse_allowed, live, 0) - fp32 [B, 4].
+ * live = 1.0f iff finished[b] == 0 at that moment (so the step that emits EOS counts, also when pad_id == eos_id) and at least one token is
+ * allowed; lse_allowed is 0 when none is.  edge_off / edge_tok / node (with n_nodes, n_edges >= 1) are optional and come together; NULL: no trie.
+ * crab_logprob_gather runs AFTER the select and before crab_advance: with y = cur_ids[b], step = step_dev[0] it writes
+ * lp[b * ld_lp + step] = z[y] - lse_raw and lp[plane_stride + b * ld_lp + step] = z[y] - lse_allowed, both 0.0f when the row was not live or y
+ * lies outside [0, V); nothing at all when step is outside [0, n_steps).  Partial sums are merged in a fixed order in double and no float
+ * atomics are used: two runs give the same bits.  Neither reads the host; both are capturable.  CRAB_E_INVALID for null operands,
+ * B / V < 1, ldl < 0, an incomplete trie, n_steps < 1, ld_lp < n_steps.
+ * ADDED under ABI 13 (crab_abi_version() still returns 13: nothing that existed changed); probe for the symbol, not for a version number. */
+int crab_logprob_norm(crab_ctx* ctx, void* stream, const float* logits, int64_t ldl, int B, int V, const int32_t* edge_off,
+                      const int32_t* edge_tok, int n_nodes, int n_edges, const int32_t* node, const int32_t* step_dev,
+                      const int32_t* finished, int eos_id, int min_new_tokens, float* norm);
+int crab_logprob_gather(crab_ctx* ctx, void* stream, const float* logits, int64_t ldl, int B, int V, const int64_t* cur_ids,
+                        const int32_t* step_dev, const float* norm, float* lp, int64_t ld_lp, int64_t plane_stride, int n_steps);
 
 /* ---------------------------------------------------------------------------------------------
  * Teacher-forced scoring (csrc/xent.hip): the language-model loss of models/modeling_llama.py:1261-1274 as reached from
