@@ -209,6 +209,8 @@ SYMBOLS = {
                                      C.c_uint64]),
     "crab_logprob_norm": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),
     "crab_logprob_gather": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i64, _i64, _i]),
+    "crab_logits_edit": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _i64, _i, _vp, _vp, _f, _i, _vp, _i, _i, _vp, _vp, _i64]),
+    "crab_logits_restore": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i64, _i]),
     "crab_lm_head_xent_workspace": (_i64, [_i, _i]),
     "crab_lm_head_xent": (_i, [_vp, _vp, _vp, _i64, _vp, _i, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _i64]),
     "crab_xent_reduce": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),

@@ -167,15 +167,71 @@ def _ws_slot(slot: int):
         ops.WS_SLOT = saved
 
 
-def _trim_at_eos(out_ids: torch.Tensor, n_done: int, eos: int) -> torch.Tensor:
+def _trim_at_eos(out_ids: torch.Tensor, n_done: int, eos) -> torch.Tensor:
     """The first n_done columns of out_ids [B, n], cut after the first column at which EVERY row has emitted `eos` (HF stops a call as soon as
-    all of its rows have finished; the columns behind it were produced between two checks).  eos < 0: no stop id.  A view: callers clone."""
+    all of its rows have finished; the columns behind it were produced between two checks).  eos < 0: no stop id; a tuple of ids (a state's
+    eos_all: eos_token_id and the stop_token_ids of its processors): any of them stops a row.  A view: callers clone."""
     out = out_ids[:, :n_done]
-    if eos >= 0:
-        idx = torch.nonzero(((out == eos).int().cumsum(1) > 0).all(0))
+    ids = [int(e) for e in (eos if isinstance(eos, (tuple, list)) else (eos,)) if int(e) >= 0]
+    if ids:
+        hit = out == ids[0]
+        for e in ids[1:]:
+            hit = hit | (out == e)
+        idx = torch.nonzero((hit.int().cumsum(1) > 0).all(0))
         if idx.numel():
             out = out[:, : int(idx[0].item()) + 1]
     return out
+
+
+def normalize_processors(processors):
+    """The `processors` argument of the generate entry points - (repetition_penalty, no_repeat_ngram_size, stop_token_ids) or None - as
+    (float, int, tuple of distinct ints in the order given) or None when every value is neutral (1.0, 0, no ids): a neutral call is the
+    call without the argument (same state key, same graph, same launches).  stop_token_ids are the stop ids BEYOND eos_token_id."""
+    if processors is None:
+        return None
+    p, n, stops = processors
+    p = 1.0 if p is None else float(p)
+    n = 0 if n is None else int(n)
+    stops = tuple(dict.fromkeys(int(e) for e in (stops or ())))
+    if not p > 0:                                           # HF: RepetitionPenaltyLogitsProcessor - "`penalty` has to be a strictly positive float"
+        raise ValueError(f"`repetition_penalty` has to be a strictly positive float, but is {p}")
+    if n < 0:                                               # HF: NoRepeatNGramLogitsProcessor - "`ngram_size` has to be a strictly positive integer" (0 = off)
+        raise ValueError(f"`no_repeat_ngram_size` has to be a positive integer or 0 (off), but is {n}")
+    if any(e < 0 for e in stops):
+        raise ValueError(f"stop_token_ids must be token ids >= 0, got {list(stops)}")
+    if len(stops) > ops.LOGITS_PROC_MAX_STOP:
+        raise NotImplementedError(f"stop_token_ids = {list(stops)}: the decode step takes at most {ops.LOGITS_PROC_MAX_STOP} stop ids beyond eos_token_id")
+    return None if (p == 1.0 and n == 0 and not stops) else (p, n, stops)
+
+
+def check_processors(processors, min_new_tokens: int = 0, constrained: bool = False, return_logprobs: bool = False, eos_token_id=None,
+                     names=("return_logprobs", "constraint", "stop_token_ids")):
+    """eos_token_id: the select's own stop id - a stop_token_id equal to it drops out first, so a triple that only repeats it is neutral.
+    names: what the caller's surface calls the three arguments in the messages (the model passes its HF-side names).
+    normalize_processors + the combinations the decode step refuses BY NAME, before any device work: each would need a change to a kernel
+    the processors leave alone (crab_logprob_norm sums plane 1 over "every token but EOS" or the trie's edges, the trie has one EOS edge).
+    The repetition penalty alone combines with everything."""
+    proc = normalize_processors(processors)
+    if isinstance(eos_token_id, (list, tuple)) and len(set(int(e) for e in eos_token_id)) == 1:
+        eos_token_id = eos_token_id[0]                          # a one-id list is that id (_state)
+    if proc is not None and isinstance(eos_token_id, int):
+        proc = normalize_processors((proc[0], proc[1], tuple(e for e in proc[2] if e != int(eos_token_id))))
+    if proc is None:
+        return None
+    p, n, stops = proc
+    lp_name, con_name, stop_name = names
+    if return_logprobs and n > 0:
+        raise NotImplementedError(f"{lp_name} with no_repeat_ngram_size = {n}: the banned tokens would have to leave the set token_logprobs_allowed is "
+                                  "normalised over (crab_logprob_norm); the repetition penalty alone is fine")
+    if return_logprobs and stops and int(min_new_tokens) > 0:
+        raise NotImplementedError(f"{lp_name} with {stop_name} = {list(stops)} and min_new_tokens = {min_new_tokens}: the suppressed stop ids would "
+                                  "have to leave the set token_logprobs_allowed is normalised over (crab_logprob_norm knows one EOS)")
+    if constrained and stops:
+        raise NotImplementedError(f"{con_name} with {stop_name} = {list(stops)}: a token trie has ONE end-of-sequence edge (pass one eos_token_id)")
+    if constrained and n > 0:
+        raise NotImplementedError(f"{con_name} with no_repeat_ngram_size = {n}: a ban could empty a trie node's edge set, which crab_constrained_select "
+                                  "reads from the trie alone")
+    return proc
 
 
 def _pack_waves(Bs: List[int], cap: int) -> List[List[int]]:
@@ -1029,12 +1085,21 @@ class GenerationEngine:
         closed-set generation) takes both among the out-edges of every row's node instead (ops.constrained_select; st.node follows the edge).
         A state with st.lp (return_logprobs) also records the log-probability of the chosen token: the normalisers of the raw logits are taken
         BEFORE the select (it sets `finished` and moves st.node), the token's logit is gathered AFTER it (ops.logprob_norm / logprob_gather); the
-        select itself is the same launch either way."""
+        select itself is the same launch either way.
+        A state with st.proc (processors: repetition penalty, n-gram ban, further stop ids) has the few logits they touch edited in place
+        between the two (ops.logits_edit) and written back right after the select (ops.logits_restore, which also marks a row that emitted a
+        further stop id as finished): the select chooses from the edited row, everything else - the logits a caller gets, both log-probability
+        planes - sees the raw one."""
         if st.lp is not None:
             tr = st.trie
             ops.logprob_norm(st.logits, st.step_dev, st.finished, st.eos, st.min_new, st.lp_norm, tr.edge_off if tr is not None else None,
                              tr.edge_tok if tr is not None else None, st.node)
+        if st.proc is not None:
+            p, n, _ = st.proc
+            ops.logits_edit(st.logits, st.out_ids, st.step_dev, st.finished, p, n, st.stop_dev, st.min_new, st.save_idx, st.save_val)
         self._select_token(st)
+        if st.proc is not None:
+            ops.logits_restore(st.logits, st.cur_ids, st.finished, st.stop_dev, st.save_idx, st.save_val)
         if st.lp is not None:
             ops.logprob_gather(st.logits, st.cur_ids, st.step_dev, st.lp_norm, st.lp)
 
@@ -1050,7 +1115,7 @@ class GenerationEngine:
             ops.sample_select(st.logits, st.cur_ids, st.out_ids, st.step_dev, st.finished, st.eos, st.pad, st.min_new, t, k, p_, seed + 7919 * st.slot)
 
     def _state(self, B: int, S: int, max_new_tokens: int, eos_token_id, pad_token_id, min_new_tokens: int, return_hidden: bool, slot: int,
-               sampling=None, ragged: bool = False, extra_key=(), constraint=None, logprobs: bool = False) -> "_DecodeState":
+               sampling=None, ragged: bool = False, extra_key=(), constraint=None, logprobs: bool = False, processors=None) -> "_DecodeState":
         """The persistent decode state of `slot` for B sequences whose (longest) prompt has S rows: KV cache, per-row words, logits and the HIP
         graph captured over them.  Kept per slot and reused by every call whose shapes, flags and buffers are the same: the key holds
         everything the captured launches bake in (pointers included).  ragged: the state of a coalesced batch (generate_many(coalesce=True)) -
@@ -1059,7 +1124,9 @@ class GenerationEngine:
         generation) - the trie's device pointers enter the key, so a captured graph never crosses tries, and every call puts the rows back on
         their roots.  logprobs: the state owns st.lp [2, B, max_new_tokens] fp32 (plane 0: log-probability of every emitted token over the
         whole vocabulary, plane 1: within the allowed set; zeroed by every call like out_ids) and st.lp_norm [B, 4], and _select fills them;
-        the flag is part of the key, so a graph captured without the two launches is never replayed for a call that wants them."""
+        the flag is part of the key, so a graph captured without the two launches is never replayed for a call that wants them.
+        processors: (repetition_penalty, no_repeat_ngram_size, stop_token_ids) or None - a non-neutral triple owns st.save_idx / st.save_val
+        (the save area of crab_logits_edit / crab_logits_restore) and st.stop_dev, and its values enter the key in the same way."""
         if int(max_new_tokens) < 1:                             # HF: GenerationConfig.validate() - "`max_new_tokens` must be greater than 0"; here the first token's slot would not exist
             raise ValueError(f"`max_new_tokens` must be greater than 0, but is {max_new_tokens}.")
         dev = self.device
@@ -1072,10 +1139,19 @@ class GenerationEngine:
         if isinstance(eos_token_id, (list, tuple)):            # HF accepts a list of stop ids (Qwen2-7B-Instruct's generation_config holds two); the device loop carries one
             if len(set(int(e) for e in eos_token_id)) > 1:
                 raise NotImplementedError(f"eos_token_id = {list(eos_token_id)}: the device-resident decode loop stops on ONE id (pass the chat end token, e.g. "
-                                          "<|im_end|>; the reference's own Qwen path never reaches HF generate, SURVEY.md 2)")
+                                          "<|im_end|>; the reference's own Qwen path never reaches HF generate, SURVEY.md 2); further stop ids go "
+                                          "into processors = (repetition_penalty, no_repeat_ngram_size, stop_token_ids)")
             eos_token_id = eos_token_id[0] if len(eos_token_id) else None
         eos = -1 if eos_token_id is None else int(eos_token_id)
-        pad = int(pad_token_id) if pad_token_id is not None else (eos if eos >= 0 else 0)
+        # processors, normalised BEFORE the key is built: a stop id equal to eos_token_id is the select's own, and a triple that is neutral
+        # after that is no triple - the call then meets the key, the graph and the launches of a call without it
+        proc = normalize_processors(processors)
+        if proc is not None:
+            proc = normalize_processors((proc[0], proc[1], tuple(e for e in proc[2] if e != eos)))
+        stops = proc[2] if proc is not None else ()
+        if proc is not None and int(max_new_tokens) > ops.LOGITS_PROC_MAX_STEPS:
+            raise NotImplementedError(f"processors with max_new_tokens = {max_new_tokens}: crab_logits_edit holds at most {ops.LOGITS_PROC_MAX_STEPS} generated tokens")
+        pad = int(pad_token_id) if pad_token_id is not None else (eos if eos >= 0 else (stops[0] if stops else 0))
         ws = self._workspace(B, slot, decode=True)
         tab = self._rope_tab(Tmax)
         # the weight mode of this state's decode steps; the FP8 forms are (re)built here, before any capture, and their pointers enter the key
@@ -1087,7 +1163,7 @@ class GenerationEngine:
                self.model.layers[0].self_attn._qkv.W.data_ptr(),
                self.model.layers[0].self_attn._qkv.RA is not None, sampling, bool(ragged),
                self._kv_mode, ks.data_ptr() if ks is not None else 0, vs.data_ptr() if vs is not None else 0, w8_key, bool(logprobs)) + tuple(extra_key) + \
-            (constraint.dev.key if constraint is not None else ())
+            (constraint.dev.key if constraint is not None else ()) + (("proc",) + proc if proc is not None else ())
         st = self._dec.get(slot)
         if st is None or st.key != key:
             st = _DecodeState()
@@ -1110,6 +1186,13 @@ class GenerationEngine:
             st.node = torch.empty((B,), device=dev, dtype=torch.int32) if constraint is not None else None
             st.lp = torch.empty((2, B, max_new_tokens), device=dev, dtype=torch.float32) if logprobs else None
             st.lp_norm = torch.zeros((B, 4), device=dev, dtype=torch.float32) if logprobs else None
+            # processors: the save area of crab_logits_edit / crab_logits_restore and the device copy of the further stop ids.  The buffers are
+            # born with the state and die with it, so the values in the key stand for their pointers as well
+            st.proc, st.eos_all = proc, (eos,) + stops
+            n_slots = 2 * int(max_new_tokens) + len(stops)
+            st.save_idx = torch.full((B, n_slots), -1, device=dev, dtype=torch.int32) if proc is not None else None
+            st.save_val = torch.zeros((B, n_slots), device=dev, dtype=torch.float32) if proc is not None else None
+            st.stop_dev = torch.tensor(stops, dtype=torch.int32).to(dev) if stops else None
             self._dec[slot] = st
         st.S = S
         st.cur_ids.zero_(); st.out_ids.fill_(pad_token_id if pad_token_id is not None else 0); st.finished.zero_()
@@ -1136,11 +1219,11 @@ class GenerationEngine:
         ops.kv_quant_fp8(sk, sv, st.kc, st.vc, st.ks, st.vs, b0=b0, t0=0, t_dst=t0, S=S, row_off=kv_start)
 
     def _start(self, embeds: torch.Tensor, max_new_tokens: int, eos_token_id, pad_token_id, min_new_tokens: int, prefill_chunk: int,
-               return_hidden: bool, slot: int, sink=None, sampling=None, constraint=None, logprobs: bool = False) -> "_DecodeState":
+               return_hidden: bool, slot: int, sink=None, sampling=None, constraint=None, logprobs: bool = False, processors=None) -> "_DecodeState":
         """Allocate the decode state of one group of sequences, prefill it and select its first token."""
         B, S, D = embeds.shape
         st = self._state(B, S, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, return_hidden, slot, sampling, constraint=constraint,
-                         logprobs=logprobs)
+                         logprobs=logprobs, processors=processors)
         # ---- prefill in chunks of sequences (bounds activation memory, keeps GEMM M in the MFMA-efficient range)
         chunks = self.plan_prefill_chunks(B, S) if not prefill_chunk else [prefill_chunk] * (B // prefill_chunk) + \
             ([B % prefill_chunk] if B % prefill_chunk else [])
@@ -1186,7 +1269,7 @@ class GenerationEngine:
             g = g1 + 1
 
     def _start_ragged(self, embeds_list: List[torch.Tensor], max_new_tokens: int, eos_token_id, pad_token_id, min_new_tokens: int,
-                      sink=None, sampling=None, return_hidden: bool = False, constraint=None, logprobs: bool = False) -> "_DecodeState":
+                      sink=None, sampling=None, return_hidden: bool = False, constraint=None, logprobs: bool = False, processors=None) -> "_DecodeState":
         """The decode state of SEVERAL generate() calls coalesced into one batch.  Group g = [B_g, S_g, D] is one call of the eval loop: its
         own prompt length and left padding, positions 0 .. S_g - 1 (unified_llama.py:262-267).  All rows share one KV cache [L, sum B_g, Hk,
         Tmax, d] in which every group is RIGHT-ALIGNED at Smax = max S_g: group g's prompt occupies slots Smax - S_g .. Smax - 1, so the token
@@ -1199,7 +1282,7 @@ class GenerationEngine:
         Ss = [int(e.shape[1]) for e in embeds_list]
         Bt, Smax = sum(Bs), max(Ss)
         st = self._state(Bt, Smax, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, return_hidden, 0, sampling, ragged=True,
-                         constraint=constraint, logprobs=logprobs)
+                         constraint=constraint, logprobs=logprobs, processors=processors)
         st.row_off.copy_(torch.tensor([Smax - S for B, S in zip(Bs, Ss) for _ in range(B)], dtype=torch.int32), non_blocking=False)
         waste = sum(B * (Smax - S) for B, S in zip(Bs, Ss)) / max(1, sum(B * S for B, S in zip(Bs, Ss)))
         if len(set(Ss)) > 1 and waste <= RAGGED_PAD_MAX:
@@ -1250,8 +1333,16 @@ class GenerationEngine:
                  pad_token_id: Optional[int] = None, min_new_tokens: int = 0, prefill_chunk: int = 0, use_graph: bool = True,
                  return_step_logits: bool = False, return_hidden: bool = False, decode_streams: int = 1,
                  return_first_logits: bool = False, sampling=None, kv_cache_dtype: Optional[str] = None, weight_dtype: Optional[str] = None,
-                 constraint=None, return_logprobs: bool = False):
+                 constraint=None, return_logprobs: bool = False, processors=None):
         """kv_cache_dtype / weight_dtype: "bf16" / "fp8_e4m3" for this call (None: the engine's); see _generate for the rest.
+        processors = (repetition_penalty, no_repeat_ngram_size, stop_token_ids) or None: HF's RepetitionPenaltyLogitsProcessor and
+        NoRepeatNGramLogitsProcessor over the GENERATED tokens (generate() with inputs_embeds starts HF from an empty input_ids, so the prompt
+        never enters them) and stop ids BEYOND eos_token_id (HF's list-valued eos_token_id: any of them finishes a row, min_new_tokens
+        suppresses all of them, finished rows emit pad_token_id - by default eos_token_id, the first id).  Applied inside the decode step
+        (csrc/logits_proc.hip: the touched logits are edited in place before the select and restored after it), greedy and sample mode alike
+        (sample mode: before the warpers, HF's order); return_step_logits and return_logprobs keep reporting the RAW logits.  Neutral values
+        (1.0, 0, no ids) are the call without the argument.  Refused by name (check_processors): return_logprobs with no_repeat_ngram_size or
+        with stop_token_ids under min_new_tokens, constraint with stop_token_ids or no_repeat_ngram_size.
         constraint = (TokenTrie, one set index per row or None): closed-set generation (crab_amd/constrain.py) - every row's ids, cut at EOS,
         are a member of the row's answer set; greedy and sample mode both choose among the trie's edges on the device, everything else (KV and
         weight modes, EOS trim, padding of finished rows) is unchanged.  A row that max_new_tokens cuts in the middle of an answer holds a
@@ -1262,10 +1353,11 @@ class GenerationEngine:
         constrained call) - HF's compute_transition_scores(normalize_logits=True) of a greedy call.  0.0 where the row emitted no token
         (padding after its EOS; the EOS column itself is a token).  Sample mode: the warpers are a drawing device and enter neither number
         (HF's warped `scores` are not reproduced).  Written inside the decode step (csrc/logprob.hip): no host sync, nothing of size B x V kept."""
+        proc = check_processors(processors, min_new_tokens, constraint is not None, return_logprobs, eos_token_id)      # refused before any device work
         cons, = self._constraints(constraint, [int(embeds.shape[0])], eos_token_id, min_new_tokens, flat=True)
         return self._call(kv_cache_dtype, weight_dtype, self._generate, embeds, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens,
                           prefill_chunk, use_graph, return_step_logits, return_hidden, decode_streams, return_first_logits, sampling, cons,
-                          return_logprobs)
+                          return_logprobs, processors=proc)
 
     def _run_steps(self, sts: List["_DecodeState"], max_new_tokens: int, graphed: bool, side_streams: bool, retire: bool, on_step=None,
                    sampled_step=None):
@@ -1288,7 +1380,7 @@ class GenerationEngine:
         if side_streams:
             for sg in streams:
                 sg.wait_stream(main)
-        eos_on = sts[0].eos >= 0
+        eos_on = any(e >= 0 for e in sts[0].eos_all)
         live = list(range(len(sts)))
         for step in range(1, max_new_tokens):
             for g in live:
@@ -1319,7 +1411,7 @@ class GenerationEngine:
     def _generate(self, embeds: torch.Tensor, max_new_tokens: int, eos_token_id: Optional[int] = None,
                   pad_token_id: Optional[int] = None, min_new_tokens: int = 0, prefill_chunk: int = 0, use_graph: bool = True,
                   return_step_logits: bool = False, return_hidden: bool = False, decode_streams: int = 1,
-                  return_first_logits: bool = False, sampling=None, constraint=None, return_logprobs: bool = False):
+                  return_first_logits: bool = False, sampling=None, constraint=None, return_logprobs: bool = False, processors=None):
         """Greedy generation from inputs_embeds only, as UnifiedForCausalLM.generate drives HF generate
         (unified_llama.py:262-267): positions 0..S-1 (left pads attended), returns ONLY new ids.
 
@@ -1336,7 +1428,8 @@ class GenerationEngine:
         groups = self.plan_batch(B, S, max_new_tokens, slots=max(1, decode_streams))
         if len(groups) > 1:
             return self._generate_split(groups, embeds, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, prefill_chunk, use_graph,
-                                        return_step_logits, return_hidden, return_first_logits, sampling, constraint, return_logprobs)
+                                        return_step_logits, return_hidden, return_first_logits, sampling, constraint, return_logprobs,
+                                        processors=processors)
         graphed = use_graph and max_new_tokens > 2
         G = decode_streams if (decode_streams > 1 and graphed and B >= decode_streams and
                                not return_step_logits and not return_hidden) else 1
@@ -1366,7 +1459,8 @@ class GenerationEngine:
             with _ws_slot(g):
                 sts.append(self._start(embeds[B * g // G:B * (g + 1) // G], max_new_tokens, eos_token_id, pad_token_id, min_new_tokens,
                                        prefill_chunk, return_hidden, g, sink, sampling,
-                                       constraint.rows(B * g // G, B * (g + 1) // G) if constraint is not None else None, return_logprobs))
+                                       constraint.rows(B * g // G, B * (g + 1) // G) if constraint is not None else None, return_logprobs,
+                                       processors=processors))
         if ops.PROFILER is not None:
             ops.PROFILER.mark("prefill_end")
         # the groups are ONE call: all of them step until all have finished (a retired group's buffer would hold the fill value, not its pad id)
@@ -1374,7 +1468,7 @@ class GenerationEngine:
         if ops.PROFILER is not None:
             ops.PROFILER.mark("decode_end")
         n_done = int(sts[0].step_dev.item())
-        out = _trim_at_eos(sts[0].out_ids if G == 1 else torch.cat([st.out_ids for st in sts], 0), n_done, sts[0].eos)
+        out = _trim_at_eos(sts[0].out_ids if G == 1 else torch.cat([st.out_ids for st in sts], 0), n_done, sts[0].eos_all)
         # st.out_ids is the persistent, graph-baked buffer the next generate() refills: hand the caller its own tensor (HF
         # generate returns fresh tensors; a caller that collects results over batches must not see them overwritten)
         res = [out.clone()]
@@ -1393,21 +1487,25 @@ class GenerationEngine:
                       pad_token_id: Optional[int] = None, min_new_tokens: int = 0, use_graph: bool = True, sampling=None,
                       return_first_logits: bool = False, coalesce: bool = False, max_rows: Optional[int] = None,
                       return_step_logits: bool = False, return_hidden: bool = False, kv_cache_dtype: Optional[str] = None,
-                      weight_dtype: Optional[str] = None, constraint=None, return_logprobs: bool = False):
+                      weight_dtype: Optional[str] = None, constraint=None, return_logprobs: bool = False, processors=None):
         """kv_cache_dtype / weight_dtype: "bf16" / "fp8_e4m3" for this call (None: the engine's); see _generate_many for the rest.
+        processors = (repetition_penalty, no_repeat_ngram_size, stop_token_ids) or None, as in generate(): every row's own generated tokens
+        are its history, wherever the row decodes (in-flight states, ragged waves).
         return_logprobs: every batch's result gains a LAST element, fp32 [B_g, n_g, 2], as in generate(); a row's scores follow the row into the
         in-flight states and the ragged waves.
         constraint = (TokenTrie, one list of set indices per batch or None): closed-set generation as in generate(); the set indices follow
         their rows into the in-flight states and the ragged waves."""
+        proc = check_processors(processors, min_new_tokens, constraint is not None, return_logprobs, eos_token_id)
         cons = self._constraints(constraint, [int(e.shape[0]) for e in embeds_list], eos_token_id, min_new_tokens) if constraint is not None else None
         return self._call(kv_cache_dtype, weight_dtype, self._generate_many, embeds_list, max_new_tokens, eos_token_id, pad_token_id,
                           min_new_tokens, use_graph, sampling, return_first_logits, coalesce, max_rows, return_step_logits, return_hidden, cons,
-                          return_logprobs)
+                          return_logprobs, processors=proc)
 
     def _generate_many(self, embeds_list: List[torch.Tensor], max_new_tokens: int, eos_token_id: Optional[int] = None,
                        pad_token_id: Optional[int] = None, min_new_tokens: int = 0, use_graph: bool = True, sampling=None,
                        return_first_logits: bool = False, coalesce: bool = False, max_rows: Optional[int] = None,
-                       return_step_logits: bool = False, return_hidden: bool = False, constraints=None, return_logprobs: bool = False):
+                       return_step_logits: bool = False, return_hidden: bool = False, constraints=None, return_logprobs: bool = False,
+                       processors=None):
         """Several INDEPENDENT batches in flight: each element of `embeds_list` ([B_i, S_i, D], its own prompt length and left padding, i.e.
         exactly what one generate() call of the reference's eval loop gets) becomes one decode group with its own KV cache, decode state
         and captured HIP graph; the groups are prefilled one after the other and their decode steps are replayed on separate HIP streams.
@@ -1436,11 +1534,12 @@ class GenerationEngine:
             raise NotImplementedError("generate_many: return_step_logits / return_hidden are options of the coalesced form, one at a time (use generate() per batch otherwise)")
         if coalesce and (G > 1 or return_step_logits or return_hidden):
             return self._generate_coalesced(embeds_list, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling,
-                                            return_first_logits, max_rows, return_step_logits, return_hidden, cons, return_logprobs)
+                                            return_first_logits, max_rows, return_step_logits, return_hidden, cons, return_logprobs,
+                                            processors=processors)
         if G == 1:
             return [self._generate(embeds_list[0], max_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id, min_new_tokens=min_new_tokens,
                                    use_graph=use_graph, sampling=sampling, return_first_logits=return_first_logits, constraint=cons[0],
-                                   return_logprobs=return_logprobs)]
+                                   return_logprobs=return_logprobs, processors=processors)]
         need = sum(e.shape[0] * self.bytes_per_sequence(e.shape[1], max_new_tokens) for e in embeds_list) + self.fixed_bytes(max(e.shape[0] for e in embeds_list),
                                                                                                                             max(e.shape[1] for e in embeds_list))
         budget = self.memory_budget(0, 0, slots=G)
@@ -1457,11 +1556,11 @@ class GenerationEngine:
         for g, emb in enumerate(embeds_list):
             with _ws_slot(g):
                 sts.append(self._start(emb, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, 0, False, g, sink, sampling, cons[g],
-                                       return_logprobs))
+                                       return_logprobs, processors=processors))
         self._run_steps(sts, max_new_tokens, use_graph and max_new_tokens > 2, True, True)
         outs = []
         for g, st in enumerate(sts):
-            out = _trim_at_eos(st.out_ids, int(st.step_dev.item()), st.eos).clone()
+            out = _trim_at_eos(st.out_ids, int(st.step_dev.item()), st.eos_all).clone()
             r = (out, firsts[g]) if return_first_logits else (out,)
             if return_logprobs:
                 r += (_lp_rows(st, 0, st.B, out.shape[1]),)
@@ -1469,7 +1568,8 @@ class GenerationEngine:
         return outs
 
     def _generate_coalesced(self, embeds_list, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling,
-                            return_first_logits, max_rows, return_step_logits=False, return_hidden=False, cons=None, return_logprobs=False):
+                            return_first_logits, max_rows, return_step_logits=False, return_hidden=False, cons=None, return_logprobs=False,
+                            processors=None):
         """generate_many(coalesce=True): pack the batches, in order, into waves of at most `cap` rows (the weight-streaming regime of the decode
         projections, and what the device's memory holds at the longest prompt), run every wave as one ragged batch."""
         Bs = [int(e.shape[0]) for e in embeds_list]
@@ -1488,19 +1588,19 @@ class GenerationEngine:
                 outs[g] = self._generate(embeds_list[g], max_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
                                          min_new_tokens=min_new_tokens, use_graph=use_graph, sampling=sampling, return_first_logits=return_first_logits,
                                          return_step_logits=return_step_logits, return_hidden=return_hidden, constraint=cons[g],
-                                         return_logprobs=return_logprobs)
+                                         return_logprobs=return_logprobs, processors=processors)
                 continue
             # the rows of the wave are the rows of its batches in wave order: so are their trie roots
             wc = _Constraint(cons[w[0]].dev, [r for g in w for r in cons[g].roots]) if cons[w[0]] is not None else None
             res = self._ragged_wave([embeds_list[g] for g in w], max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling,
-                                    return_first_logits, return_step_logits, return_hidden, wc, return_logprobs)
+                                    return_first_logits, return_step_logits, return_hidden, wc, return_logprobs, processors=processors)
             for g, r in zip(w, res):
                 outs[g] = r
         self.last_plan = plan
         return outs
 
     def _ragged_wave(self, embeds_list, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling, return_first_logits,
-                     return_step_logits=False, return_hidden=False, constraint=None, return_logprobs=False):
+                     return_step_logits=False, return_hidden=False, constraint=None, return_logprobs=False, processors=None):
         firsts, steps = [], []
 
         def sink(st):
@@ -1513,7 +1613,7 @@ class GenerationEngine:
 
         with _ws_slot(0):
             st = self._start_ragged(embeds_list, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, sink, sampling, return_hidden, constraint,
-                                    return_logprobs)
+                                    return_logprobs, processors=processors)
         if ops.PROFILER is not None:
             ops.PROFILER.mark("prefill_end")
         self._run_steps([st], max_new_tokens, use_graph and max_new_tokens > 2, False, True,
@@ -1526,7 +1626,7 @@ class GenerationEngine:
         for e in embeds_list:
             r1 = r0 + int(e.shape[0])
             # what this batch's own generate() call returns: HF stops a call as soon as all of ITS rows have finished
-            out = _trim_at_eos(st.out_ids[r0:r1], n_done, st.eos).clone()
+            out = _trim_at_eos(st.out_ids[r0:r1], n_done, st.eos_all).clone()
             if return_step_logits or return_hidden:
                 r = (out, sl[r0:r1, : out.shape[1]].clone())
             else:
@@ -1602,7 +1702,8 @@ class GenerationEngine:
     def generate_shared_prefix(self, prefix_embeds: torch.Tensor, suffix_embeds, max_new_tokens: int, eos_token_id: Optional[int] = None,
                                pad_token_id: Optional[int] = None, min_new_tokens: int = 0, use_graph: bool = True, sampling=None,
                                return_first_logits: bool = False, return_step_logits: bool = False, kv_cache_dtype: Optional[str] = None,
-                               weight_dtype: Optional[str] = None, max_rows: Optional[int] = None, constraint=None, return_logprobs: bool = False):
+                               weight_dtype: Optional[str] = None, max_rows: Optional[int] = None, constraint=None, return_logprobs: bool = False,
+                               processors=None):
         """Several questions per clip on ONE prefix KV.  prefix_embeds [C, P, D] bf16: the shared part of C clips (everything up to the question
         text; the same P for all).  suffix_embeds: C lists, one [S_cg, D] tensor per question of the clip.  Returns one id tensor per clip,
         [G_c, n] (with return_first_logits (ids, fp32 [G_c, V]); with return_step_logits (ids, fp32 [G_c, n, V])): what
@@ -1620,13 +1721,16 @@ class GenerationEngine:
         (plan_shared_prefix).  Sample mode draws per (seed, step, row of the wave), as the coalesced form does.
         kv_cache_dtype = "fp8_e4m3" and weight_dtype = "fp8_e4m3" raise NotImplementedError: the shared prefix is a bf16 path.
         constraint = (TokenTrie, one list per clip with one set index per question, or None): closed-set generation as in generate().
-        return_logprobs: every clip's result gains a LAST element, fp32 [G_c, n, 2], as in generate()."""
+        return_logprobs: every clip's result gains a LAST element, fp32 [G_c, n, 2], as in generate().
+        processors = (repetition_penalty, no_repeat_ngram_size, stop_token_ids) or None, as in generate()."""
+        proc = check_processors(processors, min_new_tokens, constraint is not None, return_logprobs, eos_token_id)
         cons = self._constraints(constraint, [len(qs) for qs in suffix_embeds], eos_token_id, min_new_tokens) if constraint is not None else None
         return self._call(kv_cache_dtype, weight_dtype, self._generate_shared_prefix, prefix_embeds, suffix_embeds, max_new_tokens, eos_token_id,
-                          pad_token_id, min_new_tokens, use_graph, sampling, return_first_logits, return_step_logits, max_rows, cons, return_logprobs)
+                          pad_token_id, min_new_tokens, use_graph, sampling, return_first_logits, return_step_logits, max_rows, cons, return_logprobs,
+                          processors=proc)
 
     def _generate_shared_prefix(self, prefix_embeds, suffix_embeds, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling,
-                                return_first_logits, return_step_logits, max_rows, cons=None, return_logprobs=False):
+                                return_first_logits, return_step_logits, max_rows, cons=None, return_logprobs=False, processors=None):
         if self._fp8:
             raise NotImplementedError('kv_cache_dtype="fp8_e4m3" with a shared prefix (generate_shared_prefix) is not implemented: the prefix cache and its attention kernels are bf16')
         if getattr(self, "_w_mode", "bf16") == "fp8_e4m3":
@@ -1645,11 +1749,11 @@ class GenerationEngine:
         for w in self.plan_shared_prefix(Gs, P, Smax, max_new_tokens, max_rows):
             wc = _Constraint(cons[w[0]].dev, [r for c in w for r in cons[c].roots]) if cons is not None else None      # one root per question, in row order
             outs += self._shared_prefix_wave(prefix_embeds[w[0]:w[-1] + 1], [suffix_embeds[c] for c in w], max_new_tokens, eos_token_id, pad_token_id,
-                                             min_new_tokens, use_graph, sampling, return_first_logits, return_step_logits, wc, return_logprobs)
+                                             min_new_tokens, use_graph, sampling, return_first_logits, return_step_logits, wc, return_logprobs, processors=processors)
         return outs
 
     def _shared_prefix_wave(self, prefix_embeds, suffix_embeds, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling,
-                            return_first_logits, return_step_logits, constraint=None, return_logprobs=False):
+                            return_first_logits, return_step_logits, constraint=None, return_logprobs=False, processors=None):
         C, P, D = prefix_embeds.shape
         Gs = [len(qs) for qs in suffix_embeds]
         flat = [q for qs in suffix_embeds for q in qs]
@@ -1674,7 +1778,7 @@ class GenerationEngine:
                 self.prefill(prefix_embeds[b0:b0 + n], px.decode.pk, px.decode.pv, b0=b0, want_logits=False)
                 b0 += n
             st = self._state(B, Smax, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, False, 0, sampling, ragged=True, extra_key=px.key,
-                             constraint=constraint, logprobs=return_logprobs)
+                             constraint=constraint, logprobs=return_logprobs, processors=processors)
             st.prefix = px.decode
             st.row_off.copy_(torch.tensor(lay["first_slot"], dtype=torch.int32))
             px.decode.rope_off.copy_(torch.tensor(lay["rope_off"], dtype=torch.int32))
@@ -1700,7 +1804,7 @@ class GenerationEngine:
         outs, r0 = [], 0
         for G in Gs:
             r1 = r0 + G
-            out = _trim_at_eos(st.out_ids[r0:r1], n_done, st.eos).clone()
+            out = _trim_at_eos(st.out_ids[r0:r1], n_done, st.eos_all).clone()
             if return_step_logits:
                 r = (out, sl[r0:r1, : out.shape[1]].clone())
             else:
@@ -1712,7 +1816,8 @@ class GenerationEngine:
         return outs
 
     def _generate_split(self, groups, embeds, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, prefill_chunk, use_graph,
-                        return_step_logits, return_hidden, return_first_logits, sampling=None, constraint=None, return_logprobs=False):
+                        return_step_logits, return_hidden, return_first_logits, sampling=None, constraint=None, return_logprobs=False,
+                        processors=None):
         """The batch does not fit the device's memory in one piece: generate the groups one after the other (rows are independent,
         so the results are those of the one-piece run up to the kernel choice a different M implies) and join them.  A group
         that finished early (EOS) is padded to the longest group's length with pad ids, like HF pads finished rows."""
@@ -1730,7 +1835,8 @@ class GenerationEngine:
                                    min_new_tokens=min_new_tokens, prefill_chunk=prefill_chunk, use_graph=use_graph,
                                    return_step_logits=return_step_logits, return_hidden=return_hidden, return_first_logits=return_first_logits,
                                    sampling=None if sampling is None else (sampling[0], sampling[1], sampling[2], sampling[3] + 104729 * b0),
-                                   constraint=constraint.rows(b0, b0 + n) if constraint is not None else None, return_logprobs=return_logprobs)
+                                   constraint=constraint.rows(b0, b0 + n) if constraint is not None else None, return_logprobs=return_logprobs,
+                                   processors=processors)
             finally:
                 self.kv_budget_bytes = saved
             parts.append(r if isinstance(r, tuple) else (r,))

@@ -744,6 +744,67 @@ def logprob_gather(logits, cur_ids, step_dev, norm, lp):
                                                _p(lp), lp.stride(1), lp.stride(0), int(lp.shape[2])), d)
 
 
+LOGITS_PROC_MAX_STOP = 8            # stop ids beyond eos_token_id that crab_logits_edit / crab_logits_restore take
+LOGITS_PROC_MAX_STEPS = 8192        # history tokens crab_logits_edit holds in LDS
+
+
+def _chk_logits_proc(logits, stop_ids, save_idx, save_val, n_slots: int):
+    B, V = logits.shape
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1 or logits.stride(0) < V:
+        # the rows are WRITTEN: a stride-0 expanded row (fine for the select kernels, which only read) would be edited B times over
+        raise ValueError(f"logits must be float32 rows with unit column stride and a row stride >= {V}, got {logits.dtype} strides {logits.stride()}")
+    n_stop = 0 if stop_ids is None else int(stop_ids.shape[0])
+    if n_stop > LOGITS_PROC_MAX_STOP:
+        raise ValueError(f"stop_ids holds {n_stop} ids, at most {LOGITS_PROC_MAX_STOP} are taken")
+    _chk_i32("stop_ids", stop_ids, n_stop, logits.device)
+    if save_idx.dtype != torch.int32 or save_idx.dim() != 2 or save_idx.shape[0] != B or save_idx.shape[1] < n_slots + n_stop or \
+            not save_idx.is_contiguous() or save_idx.device != logits.device:
+        raise ValueError(f"save_idx must be a contiguous int32 [{B}, >= {n_slots + n_stop}] tensor on {logits.device}, got {save_idx.dtype} "
+                         f"{tuple(save_idx.shape)} on {save_idx.device}")
+    _chk_f32("save_val", save_val, save_idx.shape, logits.device)
+    if not save_val.is_contiguous():
+        raise ValueError("save_val must be contiguous")
+    return n_stop
+
+
+def logits_edit(logits, out_ids, step_dev, finished, repetition_penalty: float, no_repeat_ngram_size: int, stop_ids, min_new_tokens: int,
+                save_idx, save_val):
+    """crab_logits_edit (csrc/logits_proc.hip), BEFORE the select of a decode step: the repetition penalty, the n-gram bans and - while
+    step < min_new_tokens - the bans of stop_ids, written IN PLACE into logits [B, V] fp32 (row stride >= V); the raw values of the edited
+    columns go to save_idx (int32) / save_val (fp32) [B, >= 2 * n_steps + n_stop] with n_steps = out_ids.shape[1].  History of row b:
+    out_ids[b, :step_dev[0]] (int64).  stop_ids: contiguous int32 [n_stop <= 8] or None."""
+    d = _dev(logits)
+    B, V = logits.shape
+    if out_ids.dtype != torch.int64 or out_ids.dim() != 2 or out_ids.shape[0] != B or out_ids.shape[1] < 1 or out_ids.stride(1) != 1 or \
+            out_ids.stride(0) < out_ids.shape[1] or out_ids.device != logits.device:
+        raise ValueError(f"out_ids must be an int64 [{B}, n_steps] tensor with unit column stride on {logits.device}, got {out_ids.dtype} "
+                         f"{tuple(out_ids.shape)} on {out_ids.device}")
+    n_steps = int(out_ids.shape[1])
+    n_stop = _chk_logits_proc(logits, stop_ids, save_idx, save_val, 2 * n_steps)
+    _chk_i32("finished", finished, B, logits.device)
+    _chk_i32("step_dev", step_dev, 1, logits.device)
+    _lib.check(_lib.load().crab_logits_edit(_lib.ctx(d), _stream(), _p(logits), logits.stride(0), B, V, _p(out_ids), out_ids.stride(0), n_steps,
+                                            _p(step_dev), _p(finished), float(repetition_penalty), int(no_repeat_ngram_size), _p(stop_ids), n_stop,
+                                            int(min_new_tokens), _p(save_idx), _p(save_val), save_idx.stride(0)), d)
+
+
+def logits_restore(logits, cur_ids, finished, stop_ids, save_idx, save_val, n_slots: Optional[int] = None):
+    """crab_logits_restore, AFTER the select and before logprob_gather / advance: the saved raw values go back into logits (bit for bit what
+    the lm_head wrote) and finished[b] |= cur_ids[b] in stop_ids.  n_slots: the slots logits_edit filled, 2 * n_steps + n_stop (default: all
+    columns of save_idx)."""
+    d = _dev(logits)
+    B, V = logits.shape
+    n_slots = int(save_idx.shape[1]) if n_slots is None else int(n_slots)
+    n_stop = _chk_logits_proc(logits, stop_ids, save_idx, save_val, 0)
+    if n_slots < 1 or n_slots > save_idx.shape[1]:
+        raise ValueError(f"n_slots = {n_slots} outside 1 .. {save_idx.shape[1]}")
+    if cur_ids.dtype != torch.int64 or cur_ids.dim() != 1 or cur_ids.shape[0] < B or not cur_ids.is_contiguous() or cur_ids.device != logits.device:
+        raise ValueError(f"cur_ids must be a contiguous int64 [{B}] tensor on {logits.device}, got {cur_ids.dtype} {tuple(cur_ids.shape)}")
+    _chk_i32("finished", finished, B, logits.device)
+    _lib.check(_lib.load().crab_logits_restore(_lib.ctx(d), _stream(), _p(logits), logits.stride(0), B, V, _p(cur_ids), _p(finished), _p(stop_ids),
+                                               n_stop, _p(save_idx), _p(save_val), save_idx.stride(0), n_slots), d)
+
+
 def advance(pos_dev, step_dev):
     d = _dev(pos_dev)
     _lib.check(_lib.load().crab_advance(_lib.ctx(d), _stream(), _p(pos_dev), _p(step_dev)), d)

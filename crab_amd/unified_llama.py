@@ -268,6 +268,12 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
     def generate(self, batch_input_ids=None, batch_labels=None, batch_X_modals=None, batch_task_names=None, **kwargs):
         """unified_llama.py:244-267.  kwargs understood (HF names): max_new_tokens, min_new_tokens, eos_token_id,
         pad_token_id, use_cache, do_sample (+ temperature, top_k, top_p, seed), output_logits / return_dict_in_generate (parity audits),
+        repetition_penalty, no_repeat_ngram_size (HF's two logits processors, over the GENERATED tokens: with inputs_embeds HF starts from an
+        empty input_ids, so the prompt never enters them) and a list-valued eos_token_id (any of the ids finishes a row, min_new_tokens
+        suppresses all of them, finished rows are padded with pad_token_id - by default the first id, as in HF): all three run inside the
+        decode step (csrc/logits_proc.hip), in greedy and sample mode (before the warpers, HF's order); output_logits and
+        output_token_logprobs keep reporting the raw logits.  Refused by name: output_token_logprobs with no_repeat_ngram_size, or with
+        several stop ids under min_new_tokens; allowed_sequences with several stop ids or no_repeat_ngram_size,
         kv_cache_dtype ("bf16" | "fp8_e4m3": the KV cache of this call, default the engine's - GenerationEngine(kv_cache_dtype=...)),
         weight_dtype ("bf16" | "fp8_e4m3": the decoder weights the decode steps of this call stream, default the engine's; FP8 serves decode
         batches of at most 16 rows - prefill, larger batches, lm_head, forward() and score() stay on the bf16 weights),
@@ -285,9 +291,10 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
         with normalize_logits=True of a greedy call), .sum_logprob [B], .sum_logprob_allowed [B] and .num_tokens [B] (int32: generated tokens, the
         EOS included).  Entries after a row's EOS are 0.  With do_sample the warpers (temperature, top_k, top_p) enter neither number - they
         describe the model, not the draw; HF's warped `scores` are not reproduced."""
-        self._check_generate_kwargs(kwargs)
+        self._check_generate_kwargs(kwargs, self._PROCESSOR_ARGS)
         sampling = self._sampling(kwargs)
-        constraint = self._constraint(kwargs)
+        eos, proc = self._processors(kwargs)
+        constraint = self._constraint(kwargs, eos)
         embeds = kwargs.pop("inputs_embeds", None)
         if ops.PROFILER is not None:
             ops.PROFILER.mark("encode_begin")
@@ -298,7 +305,6 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
             embeds = inputs['inputs_embeds']
         embeds = embeds.to(device=self.device, dtype=BF16)
         max_new = int(kwargs.get("max_new_tokens", 20))
-        eos = kwargs.get("eos_token_id", self.config.eos_token_id)
         pad = kwargs.get("pad_token_id", self.model.pad_token_id if self.model.pad_token_id is not None else eos)
         want_logits = bool(kwargs.get("output_logits")) and bool(kwargs.get("return_dict_in_generate"))
         want_first = bool(kwargs.get("output_first_logits"))      # not an HF name: ids + the first step's logits only (eval gather)
@@ -308,12 +314,12 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
                                     prefill_chunk=int(kwargs.get("prefill_chunk", 0)), use_graph=kwargs.get("use_graph", True),
                                     return_step_logits=want_logits, decode_streams=int(kwargs.get("decode_streams", 1)),
                                     return_first_logits=want_first, sampling=sampling, kv_cache_dtype=kwargs.get("kv_cache_dtype"), weight_dtype=kwargs.get("weight_dtype"),
-                                    constraint=constraint, return_logprobs=want_lp)
+                                    constraint=constraint, return_logprobs=want_lp, processors=proc)
         if want_logits or want_first or want_lp:
             res = list(res)
             out = type("GenerateOutput", (), {})()
             if want_lp:
-                _fill_logprob_fields(out, res[0], res.pop(), eos)
+                _fill_logprob_fields(out, res[0], res.pop(), _stop_ids(eos, proc))
             out.sequences = res.pop(0)
             if want_logits:
                 sl = res.pop(0)
@@ -335,15 +341,17 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
         throughput of one large generate(); per-batch ids / logits agree with separate calls within the decoder's bf16 tolerance.
         Returns one id tensor per batch (with output_first_logits=True: (ids, fp32 logits of the first generated position)).
         allowed_sequences / allowed_set: closed-set generation as in generate(); allowed_set is one list of set indices per batch.
+        repetition_penalty / no_repeat_ngram_size / a list-valued eos_token_id: as in generate(), per row.
         output_token_logprobs=True: every batch's result is a GenerateOutput with the fields generate() gives it (.sequences, .token_logprobs,
         .token_logprobs_allowed, .sum_logprob, .sum_logprob_allowed, .num_tokens; .first_logits with output_first_logits)."""
         for k in ("output_logits", "return_dict_in_generate", "inputs_embeds"):
             if kwargs.get(k) is not None and kwargs.get(k) is not False:
                 raise NotImplementedError(f"generate_batches returns token ids only: {k} is a generate() argument")
         want_first = bool(kwargs.get("output_first_logits"))
-        self._check_generate_kwargs(kwargs)
+        self._check_generate_kwargs(kwargs, self._PROCESSOR_ARGS)
         sampling = self._sampling(kwargs)
-        constraint = self._constraint(kwargs)
+        eos, proc = self._processors(kwargs)
+        constraint = self._constraint(kwargs, eos)
         if ops.PROFILER is not None:
             ops.PROFILER.mark("encode_begin")
         if coalesce:
@@ -356,15 +364,14 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
                                                         batch_X_modals=b["batch_X_modals"], return_multi_scale_features=False, return_gt_mask=False,
                                                         batch_task_names=b.get("batch_task_names"))
                 embeds.append(inputs['inputs_embeds'].to(device=self.device, dtype=BF16))
-        eos = kwargs.get("eos_token_id", self.config.eos_token_id)
         pad = kwargs.get("pad_token_id", self.model.pad_token_id if self.model.pad_token_id is not None else eos)
         want_lp = bool(kwargs.get("output_token_logprobs"))
         res = self._engine.generate_many(embeds, int(kwargs.get("max_new_tokens", 20)), eos_token_id=eos, pad_token_id=pad,
                                          min_new_tokens=int(kwargs.get("min_new_tokens", 0) or 0), use_graph=kwargs.get("use_graph", True),
                                          sampling=sampling, return_first_logits=want_first, coalesce=coalesce, max_rows=max_rows,
                                          kv_cache_dtype=kwargs.get("kv_cache_dtype"), weight_dtype=kwargs.get("weight_dtype"), constraint=constraint,
-                                         return_logprobs=want_lp)
-        return [_logprob_output(r, want_first, eos) for r in res] if want_lp else res
+                                         return_logprobs=want_lp, processors=proc)
+        return [_logprob_output(r, want_first, _stop_ids(eos, proc)) for r in res] if want_lp else res
 
     @torch.no_grad()
     def generate_questions(self, clips, max_rows: Optional[int] = None, **kwargs):
@@ -378,15 +385,17 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
         what generate() returns for the ids cat(shared, question g), within the decoder's bf16 tolerance (with output_first_logits=True:
         (ids, fp32 logits of the first generated position)).
         allowed_sequences / allowed_set: closed-set generation as in generate(); allowed_set is one list per clip with one set index per question.
+        repetition_penalty / no_repeat_ngram_size / a list-valued eos_token_id: as in generate(), per question.
         output_token_logprobs=True: every clip's result is a GenerateOutput as generate_batches returns it (one row per question)."""
         for k in ("output_logits", "return_dict_in_generate", "inputs_embeds"):
             if kwargs.get(k) is not None and kwargs.get(k) is not False:
                 raise NotImplementedError(f"generate_questions returns token ids only: {k} is a generate() argument")
         want_first = bool(kwargs.get("output_first_logits"))
         want_lp = bool(kwargs.get("output_token_logprobs"))
-        self._check_generate_kwargs(kwargs)
+        self._check_generate_kwargs(kwargs, self._PROCESSOR_ARGS)
         sampling = self._sampling(kwargs)
-        constraint = self._constraint(kwargs)
+        eos, proc = self._processors(kwargs)
+        constraint = self._constraint(kwargs, eos)
         if constraint is not None and constraint[1] is not None and len(constraint[1]) != len(clips):
             raise ValueError(f"allowed_set: {len(constraint[1])} lists of set indices for {len(clips)} clips")
         if ops.PROFILER is not None:
@@ -400,7 +409,6 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
                                                     batch_task_names=c.get("batch_task_names"))
             prefixes.append(inputs['inputs_embeds'].to(device=self.device, dtype=BF16))
             questions.append([self.encode_ids(torch.as_tensor(q, device=self.device).reshape(-1)).to(BF16) for q in c["question_ids"]])
-        eos = kwargs.get("eos_token_id", self.config.eos_token_id)
         pad = kwargs.get("pad_token_id", self.model.pad_token_id if self.model.pad_token_id is not None else eos)
         outs = [None] * len(clips)
         for P in sorted({p.shape[1] for p in prefixes}):
@@ -412,9 +420,9 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
                                                       weight_dtype=kwargs.get("weight_dtype"), max_rows=max_rows,
                                                       constraint=None if constraint is None else
                                                       (constraint[0], None if constraint[1] is None else [constraint[1][i] for i in idx]),
-                                                      return_logprobs=want_lp)
+                                                      return_logprobs=want_lp, processors=proc)
             for i, r in zip(idx, res):
-                outs[i] = _logprob_output(r, want_first, eos) if want_lp else r
+                outs[i] = _logprob_output(r, want_first, _stop_ids(eos, proc)) if want_lp else r
         return outs
 
     # HF generate() arguments that would CHANGE what is decoded and that this path does not implement: refused by name instead of ignored
@@ -427,9 +435,15 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
                     "forced_bos_token_id": None, "forced_eos_token_id": None, "assistant_model": None, "streamer": None, "max_time": None,
                     "stop_strings": None, "min_p": None, "guidance_scale": None, "sequence_bias": None}
 
+    # the names of _UNSUPPORTED that the decode step implements (csrc/logits_proc.hip): an entry point that routes them to the engine says so
+    _PROCESSOR_ARGS = frozenset(("repetition_penalty", "no_repeat_ngram_size"))
+
     @classmethod
-    def _check_generate_kwargs(cls, kwargs):
+    def _check_generate_kwargs(cls, kwargs, implemented=frozenset()):
+        """implemented: the names of _UNSUPPORTED the calling entry point hands to the engine; a bare call refuses them like the rest."""
         for k, off in cls._UNSUPPORTED.items():
+            if k in implemented:
+                continue
             v = kwargs.get(k, off)
             if v is None or v == off or (isinstance(v, (list, tuple)) and len(v) == 0):
                 continue
@@ -438,16 +452,33 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
         if "max_length" in kwargs and kwargs.get("max_length") is not None and kwargs.get("max_new_tokens") is None:
             raise NotImplementedError("generate(max_length=...): with inputs_embeds only HF counts new tokens alone - pass max_new_tokens")
 
-    def _constraint(self, kwargs):
-        """allowed_sequences / allowed_set -> the engine's constraint argument (TokenTrie, set indices) or None.  eos_token_id and
-        min_new_tokens are checked against the trie here, before any device work (ValueError by name)."""
+    def _processors(self, kwargs):
+        """repetition_penalty / no_repeat_ngram_size / eos_token_id -> (the engine's ONE eos_token_id, its processors triple or None).  A
+        list-valued eos_token_id (HF: any of the ids stops a row) gives the first id to the select kernels and the distinct rest, as
+        stop_token_ids, to the processors; the refused combinations raise here, before any device work (decoder.check_processors)."""
+        from .decoder import check_processors
+        eos = kwargs.get("eos_token_id", self.config.eos_token_id)
+        stops = ()
+        if torch.is_tensor(eos):
+            eos = eos.reshape(-1).tolist()
+        if isinstance(eos, (list, tuple)):
+            ids = list(dict.fromkeys(int(e) for e in eos))
+            eos, stops = (ids[0] if ids else None), tuple(ids[1:])
+        proc = check_processors((kwargs.get("repetition_penalty"), kwargs.get("no_repeat_ngram_size"), stops), int(kwargs.get("min_new_tokens", 0) or 0),
+                                kwargs.get("allowed_sequences") is not None, bool(kwargs.get("output_token_logprobs")), eos,
+                                names=("output_token_logprobs", "allowed_sequences", "eos_token_id beyond the first"))      # the names the caller passed
+        return eos, proc
+
+    def _constraint(self, kwargs, eos=None):
+        """allowed_sequences / allowed_set -> the engine's constraint argument (TokenTrie, set indices) or None.  eos_token_id (eos: the ONE id
+        _processors made of it) and min_new_tokens are checked against the trie here, before any device work (ValueError by name)."""
         seqs = kwargs.get("allowed_sequences")
         if seqs is None:
             if kwargs.get("allowed_set") is not None:
                 raise ValueError("allowed_set names answer sets of allowed_sequences, which is missing")
             return None
         from .constrain import as_trie
-        trie = as_trie(seqs, self.lm_head.weight.shape[0], kwargs.get("eos_token_id", self.config.eos_token_id), int(kwargs.get("min_new_tokens", 0) or 0))
+        trie = as_trie(seqs, self.lm_head.weight.shape[0], eos, int(kwargs.get("min_new_tokens", 0) or 0))
         if kwargs.get("allowed_set") is None and trie.n_sets > 1:
             raise ValueError(f"allowed_sequences holds {trie.n_sets} sets, so every row needs a set index: pass allowed_set")
         return (trie, kwargs.get("allowed_set"))
@@ -486,7 +517,7 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
             samples = [{"batch_input_ids": [batch_input_ids[i]], "batch_labels": [batch_labels[i]] if batch_labels is not None else None,
                         "batch_X_modals": [batch_X_modals[i]], "batch_task_names": [batch_task_names[i]]} for i in range(len(batch_input_ids))]
             res = self.generate_avs_many(samples, **kwargs)
-            eos = kwargs.get("eos_token_id", self.config.eos_token_id)
+            eos, _ = self._processors(kwargs)                  # a list-valued eos_token_id: the first id (HF pads with it)
             pad = kwargs.get("pad_token_id", self.model.pad_token_id if self.model.pad_token_id is not None else eos)
             n_max = max(r['output_ids'].shape[1] for r in res)
             ids = torch.full((len(res), n_max), int(pad if pad is not None else 0), device=res[0]['output_ids'].device, dtype=res[0]['output_ids'].dtype)
@@ -528,18 +559,18 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
 
     def _avs_generate(self, samples, max_rows, kwargs):
         """First half of generate_avs_many: inputs of every call (multi-scale CLIP features kept) and the ragged decode with per-step hidden states."""
-        self._check_generate_kwargs(kwargs)
+        self._check_generate_kwargs(kwargs, self._PROCESSOR_ARGS)
         sampling = self._sampling(kwargs)
+        eos, proc = self._processors(kwargs)
         if ops.PROFILER is not None:
             ops.PROFILER.mark("encode_begin")
         inputs = self.prepare_multimodal_inputs_many(samples, return_multi_scale_features=True, return_gt_mask=True)
         embeds = [d['inputs_embeds'].to(device=self.device, dtype=BF16) for d in inputs]
-        eos = kwargs.get("eos_token_id", self.config.eos_token_id)
         pad = kwargs.get("pad_token_id", self.model.pad_token_id if self.model.pad_token_id is not None else eos)
         outs = self._engine.generate_many(embeds, int(kwargs.get("max_new_tokens", 20)), eos_token_id=eos, pad_token_id=pad,
                                           min_new_tokens=int(kwargs.get("min_new_tokens", 0) or 0), use_graph=kwargs.get("use_graph", True),
                                           sampling=sampling, coalesce=True, max_rows=max_rows, return_hidden=True,
-                                          kv_cache_dtype=kwargs.get("kv_cache_dtype"), weight_dtype=kwargs.get("weight_dtype"))
+                                          kv_cache_dtype=kwargs.get("kv_cache_dtype"), weight_dtype=kwargs.get("weight_dtype"), processors=proc)
         return inputs, outs
 
     def _avs_segment(self, samples, inputs, outs, chosen):
@@ -564,18 +595,25 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
         return r
 
 
+def _stop_ids(eos, proc):
+    """Every id that ends a row: the engine's eos_token_id and the stop_token_ids of its processors triple."""
+    return ([] if eos is None else [int(eos)]) + (list(proc[2]) if proc is not None else [])
+
+
 def _fill_logprob_fields(out, ids: torch.Tensor, lp: torch.Tensor, eos):
     """The output_token_logprobs fields of a GenerateOutput from the engine's scores lp [B, n, 2] (GenerationEngine.generate(return_logprobs)):
-    names as in ScoreOutput.  num_tokens counts a row's ids up to and including its first EOS (all n without one)."""
+    names as in ScoreOutput.  num_tokens counts a row's ids up to and including its first EOS (all n without one); eos may be a list of stop
+    ids (_stop_ids): the first of ANY of them is the row's last token."""
     out.token_logprobs, out.token_logprobs_allowed = lp[..., 0].contiguous(), lp[..., 1].contiguous()
     out.sum_logprob, out.sum_logprob_allowed = out.token_logprobs.sum(1), out.token_logprobs_allowed.sum(1)
     n = ids.shape[1]
-    if isinstance(eos, (list, tuple)):
-        eos = eos[0] if len(eos) else None
-    if eos is None or n == 0:
+    stops = [int(e) for e in (eos if isinstance(eos, (list, tuple)) else (eos,)) if e is not None]
+    if not stops or n == 0:
         out.num_tokens = torch.full((ids.shape[0],), n, device=ids.device, dtype=torch.int32)
     else:
-        hit = ids == int(eos)
+        hit = ids == stops[0]
+        for e in stops[1:]:
+            hit = hit | (ids == e)
         first = torch.where(hit.any(1), hit.to(torch.int32).argmax(1) + 1, torch.full_like(ids[:, 0], n))
         out.num_tokens = first.to(torch.int32)
 

@@ -457,6 +457,31 @@ int crab_logprob_norm(crab_ctx* ctx, void* stream, const float* logits, int64_t 
                       const int32_t* finished, int eos_id, int min_new_tokens, float* norm);
 int crab_logprob_gather(crab_ctx* ctx, void* stream, const float* logits, int64_t ldl, int B, int V, const int64_t* cur_ids,
                         const int32_t* step_dev, const float* norm, float* lp, int64_t ld_lp, int64_t plane_stride, int n_steps);
+/* Logits processors of the step (csrc/logits_proc.hip): HF's RepetitionPenaltyLogitsProcessor, NoRepeatNGramLogitsProcessor and several stop
+ * ids (MinNewTokensLengthLogitsProcessor with a list, EosTokenCriteria) without a host callback and without a [B, V] copy: the few columns a
+ * processor touches are edited IN PLACE before the select and written back after it.  History of row b: h[j] = out_ids[b, j] for
+ * j < step = step_dev[0] (clamped to [0, n_steps]) - generated tokens only, as HF sees them when generate() is driven with inputs_embeds.
+ * crab_logits_edit runs BEFORE the select (and after crab_logprob_norm): one block per row; a row with finished[b] != 0 is left alone.
+ *     save     (column, raw value) of every edit goes to the save area, int32 save_idx / fp32 save_val [B, ld_save], fixed slots: j < n_steps the
+ *              penalty edit of history token j, n_steps + j the ban of n-gram window j, 2 n_steps + e stop id e; a slot without an edit holds
+ *              (-1, 0).  All 2 n_steps + n_stop slots of every row are written by every launch, all raw values before any edit.
+ *     penalty  repetition_penalty p != 1: for the first occurrence of every distinct history token x = x < 0 ? x * p : x / p (a true fp32
+ *              division: the bits of torch.where(score < 0, score * p, score / p)).
+ *     bans     -inf: with n = no_repeat_ngram_size > 0 and step + 1 >= n, the token h[j + n - 1] of every window j in [0, step - n] whose
+ *              first n - 1 tokens equal the last n - 1 of the history (n = 1: every seen token); while step < min_new_tokens, every stop_ids[e].
+ * Every id read from device memory is checked against [0, V): a bad id is never edited and equals nothing in an n-gram comparison.
+ * crab_logits_restore runs AFTER the select and before crab_logprob_gather / crab_advance: the n_slots = 2 n_steps + n_stop saved values go
+ * back (the logits are then bit for bit what they were) and finished[b] |= (cur_ids[b] is one of stop_ids).  The select kernels keep their one
+ * eos_id; stop_ids are the ids beyond it (NULL with n_stop = 0).  Neither launch reads the host; both are capturable; no atomics.
+ * CRAB_E_INVALID for null operands, B / V / n_steps < 1, ldl < V (the rows are written), ld_out < n_steps, repetition_penalty <= 0,
+ * no_repeat_ngram_size < 0, n_stop outside 0 .. 8, ld_save < 2 n_steps + n_stop (restore: n_slots < 1 or ld_save < n_slots).
+ * CRAB_E_UNSUPPORTED for n_steps > 8192: the history is held in LDS as int32 (32 KB).
+ * ADDED under ABI 13 (crab_abi_version() still returns 13: nothing that existed changed); probe for the symbol, not for a version number. */
+int crab_logits_edit(crab_ctx* ctx, void* stream, float* logits, int64_t ldl, int B, int V, const int64_t* out_ids, int64_t ld_out,
+                     int n_steps, const int32_t* step_dev, const int32_t* finished, float repetition_penalty, int no_repeat_ngram_size,
+                     const int32_t* stop_ids, int n_stop, int min_new_tokens, int32_t* save_idx, float* save_val, int64_t ld_save);
+int crab_logits_restore(crab_ctx* ctx, void* stream, float* logits, int64_t ldl, int B, int V, const int64_t* cur_ids, int32_t* finished,
+                        const int32_t* stop_ids, int n_stop, const int32_t* save_idx, const float* save_val, int64_t ld_save, int n_slots);
 
 /* ---------------------------------------------------------------------------------------------
  * Teacher-forced scoring (csrc/xent.hip): the language-model loss of models/modeling_llama.py:1261-1274 as reached from
