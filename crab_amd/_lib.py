@@ -211,6 +211,12 @@ SYMBOLS = {
     "crab_logprob_gather": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i64, _i64, _i]),
     "crab_logits_edit": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _i64, _i, _vp, _vp, _f, _i, _vp, _i, _i, _vp, _vp, _i64]),
     "crab_logits_restore": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i64, _i]),
+    "crab_beam_max": (_i, []),
+    "crab_beam_max_new": (_i, []),
+    "crab_beam_row_topk": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "crab_beam_merge": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
+                             _vp, _vp]),
+    "crab_kv_beam_reorder": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "crab_lm_head_xent_workspace": (_i64, [_i, _i]),
     "crab_lm_head_xent": (_i, [_vp, _vp, _vp, _i64, _vp, _i, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _i64]),
     "crab_xent_reduce": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
@@ -294,7 +300,8 @@ def load() -> C.CDLL:
                 raise CrabHipError(f"libcrab_hip.so does not export {name}")
             fn.restype = res
             fn.argtypes = args
-        for macro, fn in (("CRAB_DECODE_MAX_ROWS", lib.crab_decode_max_rows), ("CRAB_ATTN_SPLIT_BELOW", lib.crab_attn_split_below)):
+        for macro, fn in (("CRAB_DECODE_MAX_ROWS", lib.crab_decode_max_rows), ("CRAB_ATTN_SPLIT_BELOW", lib.crab_attn_split_below),
+                          ("CRAB_BEAM_MAX", lib.crab_beam_max), ("CRAB_BEAM_MAX_NEW", lib.crab_beam_max_new)):
             if fn() != header_const(macro):
                 raise CrabHipError(f"libcrab_hip.so was built with {macro} = {fn()}, include/crab_hip.h says {header_const(macro)}: rebuild (csrc/build.sh)")
         _lib = lib

@@ -1089,7 +1089,16 @@ class GenerationEngine:
         A state with st.proc (processors: repetition penalty, n-gram ban, further stop ids) has the few logits they touch edited in place
         between the two (ops.logits_edit) and written back right after the select (ops.logits_restore, which also marks a row that emitted a
         further stop id as finished): the select chooses from the edited row, everything else - the logits a caller gets, both log-probability
-        planes - sees the raw one."""
+        planes - sees the raw one.
+        A state with st.beam (generate_beam) takes none of these: its select is the beam step (csrc/beam.hip)."""
+        if st.beam is not None:
+            # beam search (generate_beam): the select is the beam step - the rows' best 2K continuations, the clip's merge (HF's steps c-g), then
+            # the own cache rows follow their parents; `finished` carries the clip's done flag, so the EOS check of _run_steps works unchanged
+            bs = st.beam
+            ops.beam_row_topk(st.logits, bs, st.step_dev, st.finished, st.eos, st.min_new)
+            ops.beam_merge(bs, st.logits.shape[1], st.step_dev, st.eos, st.cur_ids, st.out_ids, st.finished)
+            ops.kv_beam_reorder(st.kc, st.vc, bs.K, bs.beam_idx, st.finished, st.pos_dev)
+            return
         if st.lp is not None:
             tr = st.trie
             ops.logprob_norm(st.logits, st.step_dev, st.finished, st.eos, st.min_new, st.lp_norm, tr.edge_off if tr is not None else None,
@@ -1182,6 +1191,7 @@ class GenerationEngine:
             st.eos, st.pad, st.min_new, st.want_hidden = eos, pad, int(min_new_tokens), bool(return_hidden)
             st.sampling = sampling
             st.prefix = None
+            st.beam = None                                     # generate_beam: the ops.BeamState born with the state (its parameters are in extra_key)
             st.trie = constraint.dev if constraint is not None else None
             st.node = torch.empty((B,), device=dev, dtype=torch.int32) if constraint is not None else None
             st.lp = torch.empty((2, B, max_new_tokens), device=dev, dtype=torch.float32) if logprobs else None
@@ -1815,6 +1825,125 @@ class GenerationEngine:
             r0 = r1
         return outs
 
+    # ------------------------------------------------------------------ beam search: the beams of a clip on one prefix KV
+    @torch.no_grad()
+    def generate_beam(self, embeds: torch.Tensor, num_beams: int, max_new_tokens: int, eos_token_id: Optional[int] = None,
+                      pad_token_id: Optional[int] = None, min_new_tokens: int = 0, length_penalty: float = 1.0, early_stopping=False,
+                      num_return_sequences: int = 1, use_graph: bool = True, max_rows: Optional[int] = None, return_scores: bool = False,
+                      trace: Optional[list] = None, **refused):
+        """HF beam search (GenerationMixin._beam_search: num_beams, length_penalty, early_stopping in {False, True, "never"},
+        num_return_sequences, min_new_tokens) from inputs_embeds [B, S, D], S >= 2.  Returns the NEW ids [B * num_return_sequences, n]: per clip
+        its hypotheses best first, pad_token_id after a hypothesis's EOS, n the longest returned; with return_scores also sequences_scores, fp32
+        [B * num_return_sequences] (sum of log-probs / len ** length_penalty).
+
+        Built on the shared-prefix wave: the first S - 1 rows of a clip are prefilled and stored ONCE (HF expands to B x K full sequences and
+        index_selects the whole cache every step); the K beams are K rows of the ragged decode state whose own cache starts with the last
+        prompt row, and only these own keys - at most max_new_tokens slots - move when beams are reordered (crab_kv_beam_reorder).  The step is
+        the ordinary decode step with the select replaced by crab_beam_row_topk -> crab_beam_merge (csrc/beam.hip), captured and replayed like
+        every other; a clip that is done is frozen, the call ends when all are.  More rows than a decode step takes run as waves of whole clips.
+        Deviations from HF: ONE eos id; no logits processors in beam mode; ties between equal scores go to the lower index (torch.topk leaves
+        them open).  num_beams = 1 is HF's one-beam search, which is greedy.
+        trace: a debugging aid - a list that receives, after the first token and after every step, a dict of clones: "step", "logits" (the
+        step's raw logits), "before" / "after" (cur_ids, run_seq, finished and every ops.BeamState field around the step); the tests replay
+        the steps from it.
+        Refused by name before any device work: num_beams outside 1 .. ops.BEAM_MAX, num_return_sequences > num_beams, S < 2, several eos ids,
+        max_new_tokens > ops.BEAM_MAX_NEW, sampling / constraint / processors / return_logprobs / return_hidden, and both FP8 modes."""
+        for name, v in refused.items():
+            if name not in ("sampling", "constraint", "processors", "return_logprobs", "return_hidden", "return_step_logits", "return_first_logits",
+                            "kv_cache_dtype", "weight_dtype"):
+                raise TypeError(f"generate_beam() got an unexpected keyword argument {name!r}")
+            if name in ("kv_cache_dtype", "weight_dtype"):
+                if v not in (None, "bf16"):
+                    raise NotImplementedError(f'{name}="{v}" with beam search (generate_beam) is not implemented: the shared prefix is a bf16 path')
+            elif v is not None and v is not False:
+                raise NotImplementedError(f"generate_beam({name}=...): not implemented in beam mode")
+        K, R = int(num_beams), int(num_return_sequences)
+        if not 1 <= K <= ops.BEAM_MAX:
+            raise NotImplementedError(f"num_beams = {num_beams}: 1 .. {ops.BEAM_MAX} beams are implemented")
+        if not 1 <= R <= K:
+            raise ValueError(f"`num_return_sequences` ({num_return_sequences}) has to be between 1 and `num_beams` ({K})")
+        if embeds.dim() != 3 or embeds.shape[1] < 2:
+            raise ValueError(f"generate_beam: embeds must be [B, S, D] with S >= 2 (the prefix needs one row), got {tuple(embeds.shape)}")
+        if isinstance(eos_token_id, (list, tuple)):
+            if len(set(int(e) for e in eos_token_id)) > 1:
+                raise NotImplementedError(f"eos_token_id = {list(eos_token_id)}: beam search stops on ONE id")
+            eos_token_id = eos_token_id[0] if len(eos_token_id) else None
+        if int(max_new_tokens) < 1:
+            raise ValueError(f"`max_new_tokens` must be greater than 0, but is {max_new_tokens}.")
+        if int(max_new_tokens) > ops.BEAM_MAX_NEW:
+            raise NotImplementedError(f"max_new_tokens = {max_new_tokens} with beam search: at most {ops.BEAM_MAX_NEW}")
+        if early_stopping not in (False, True, "never"):
+            raise ValueError(f'early_stopping must be False, True or "never", got {early_stopping!r}')
+        if 2 * K > self.lm_head.weight.shape[0]:
+            raise ValueError(f"num_beams = {K}: the vocabulary holds fewer than 2 num_beams tokens")
+        if self._fp8:
+            raise NotImplementedError('kv_cache_dtype="fp8_e4m3" with beam search (generate_beam) is not implemented: the prefix cache and its attention kernels are bf16')
+        if getattr(self, "_w_mode", "bf16") == "fp8_e4m3":
+            raise NotImplementedError('weight_dtype="fp8_e4m3" with beam search (generate_beam) is not implemented')
+        return self._call(None, None, self._generate_beam, embeds, K, int(max_new_tokens), eos_token_id, pad_token_id, int(min_new_tokens),
+                          float(length_penalty), early_stopping, R, use_graph, max_rows, return_scores, trace)
+
+    def _generate_beam(self, embeds, K, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, length_penalty, early_stopping, R, use_graph,
+                       max_rows, return_scores, trace):
+        embeds = embeds.to(device=self.device, dtype=BF16)
+        B, S, D = embeds.shape
+        seqs, scores, lens = [], [], []
+        for w in self.plan_shared_prefix([K] * B, S - 1, 1, max_new_tokens, max_rows):
+            hs, sc, ln = self._beam_wave(embeds[w[0]:w[-1] + 1], K, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, length_penalty,
+                                         early_stopping, use_graph, trace)
+            seqs.append(hs[:, :R]); scores.append(sc[:, :R]); lens.append(ln[:, :R])
+        seqs, scores, lens = torch.cat(seqs, 0), torch.cat(scores, 0), torch.cat(lens, 0)
+        n = max(1, int(lens.max().item()))
+        ids = seqs[:, :, :n].reshape(B * R, n).contiguous()
+        return (ids, scores.reshape(B * R).contiguous()) if return_scores else ids
+
+    def _beam_wave(self, embeds, K, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, length_penalty, early_stopping, use_graph, trace):
+        """One wave of whole clips: prefix = all but the last prompt row, once per clip; the K beams of a clip are K copies of the last row.
+        Returns fresh (hyp_seq [C, K, max_new], hyp_score [C, K], hyp_len [C, K])."""
+        C, S, D = embeds.shape
+        P, rows = S - 1, C * K
+        lay = shared_prefix_layout(P, [1] * rows, max_new_tokens)
+        Tmax = lay["Tmax"]
+        self._rope_tab(P + Tmax)
+        px = self._shared_prefix_buffers(C, P, [K] * C, 1)
+        with _ws_slot(0):
+            b0 = 0
+            for n in self.plan_prefill_chunks(C, P):
+                self.prefill(embeds[b0:b0 + n, :P], px.decode.pk, px.decode.pv, b0=b0, want_logits=False)
+                b0 += n
+            st = self._state(rows, 1, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, False, 0, None, ragged=True,
+                             extra_key=px.key + ("beam", K, float(length_penalty), early_stopping))
+            if st.beam is None:
+                st.beam = ops.BeamState(C, K, max_new_tokens, st.pad, length_penalty, early_stopping, self.device)
+            else:
+                st.beam.reset()
+            st.out_ids.fill_(st.pad)                           # the running histories: HF's fill value
+            st.prefix = px.decode
+            st.row_off.copy_(torch.tensor(lay["first_slot"], dtype=torch.int32))
+            px.decode.rope_off.copy_(torch.tensor(lay["rope_off"], dtype=torch.int32))
+            ws = self._workspace(rows)
+            last = embeds[:, P:].expand(C, K, D).reshape(rows, D).contiguous()
+            ops.cast_rows(last, ws.x, rows, D)
+            x, hfin = self._layers(ws, rows, 1, st.kc, st.vc, 0, Tmax, 0, None, None, row_off=st.row_off, prefix=px.decode)
+            ops.copy_rows(hfin, st.hn, rows, D)
+            ops.gemm(st.hn, self.lm_head.weight, out=st.logits, out_fp32=True)
+            snap = lambda: dict(st.beam.snapshot(), cur_ids=st.cur_ids.clone(), run_seq=st.out_ids.clone(), finished=st.finished.clone())
+            prev = [snap()] if trace is not None else None
+
+            def sink(s):
+                if trace is not None:
+                    after = snap()
+                    trace.append({"step": len(trace_steps), "logits": s.logits.clone(), "before": prev[0], "after": after})
+                    trace_steps.append(0)
+                    prev[0] = after
+
+            trace_steps = []
+            self._first_token(st)
+            sink(st)
+        self._run_steps([st], max_new_tokens, use_graph and max_new_tokens > 2, False, True, sink if trace is not None else None)
+        bs = st.beam
+        return (bs.hyp_seq.view(C, K, max_new_tokens).clone(), bs.hyp_score.view(C, K).clone(), bs.hyp_len.view(C, K).clone())
+
     def _generate_split(self, groups, embeds, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, prefill_chunk, use_graph,
                         return_step_logits, return_hidden, return_first_logits, sampling=None, constraint=None, return_logprobs=False,
                         processors=None):
@@ -1864,6 +1993,8 @@ class GenerationEngine:
         # warm-up run outside capture is not possible without mutating state; instead snapshot and restore
         snap = (st.cur_ids.clone(), st.out_ids.clone(), st.finished.clone(), st.pos_dev.clone(), st.step_dev.clone(),
                 st.node.clone() if st.node is not None else None)
+        if st.beam is not None:
+            st.finished.fill_(1)                       # a beam step permutes its state and the cache in place: the warm-up runs with every clip done (frozen)
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):

@@ -805,6 +805,101 @@ def logits_restore(logits, cur_ids, finished, stop_ids, save_idx, save_val, n_sl
                                                n_stop, _p(save_idx), _p(save_val), save_idx.stride(0), n_slots), d)
 
 
+BEAM_MAX = _lib.header_const("CRAB_BEAM_MAX")                # beams per clip
+BEAM_MAX_NEW = _lib.header_const("CRAB_BEAM_MAX_NEW")        # max_new_tokens of a beam call
+BEAM_EARLY = {False: 0, True: 1, "never": 2}
+
+
+def beam_len_table(max_new: int, length_penalty: float) -> torch.Tensor:
+    """fp32 [max_new + 1]: n ** length_penalty as HF's Python scalar gives it (a double pow), rounded to fp32 once; entry 0 is unused."""
+    return torch.tensor([1.0] + [float(n) ** float(length_penalty) for n in range(1, int(max_new) + 1)], dtype=torch.float64).to(torch.float32)
+
+
+class BeamState:
+    """The device-resident beam state of `clips` x K rows (include/crab_hip.h "Beam search"): everything crab_beam_row_topk / crab_beam_merge /
+    crab_kv_beam_reorder read and write beside the decode state's own cur_ids, out_ids (= run_seq), finished and step_dev.  reset() puts back
+    HF's initial values.  length_penalty / early_stopping are fixed per state (len_tab is built from them)."""
+
+    FIELDS = ("run_score", "hyp_score", "hyp_seq", "hyp_len", "hyp_fin", "unsat", "beam_idx")
+
+    def __init__(self, clips: int, K: int, max_new: int, pad: int, length_penalty: float, early_stopping, device):
+        if early_stopping not in (False, True, "never"):
+            raise ValueError(f'early_stopping must be False, True or "never", got {early_stopping!r}')
+        rows = clips * K
+        self.clips, self.K, self.max_new, self.pad = int(clips), int(K), int(max_new), int(pad)
+        self.length_penalty, self.early_stopping = float(length_penalty), early_stopping
+        self.early = BEAM_EARLY[early_stopping if isinstance(early_stopping, str) else bool(early_stopping)]
+        self.len_tab = beam_len_table(max_new, length_penalty).to(device)
+        self.run_score = torch.empty((rows,), device=device, dtype=torch.float32)
+        self.hyp_score = torch.empty((rows,), device=device, dtype=torch.float32)
+        self.hyp_seq = torch.empty((rows, max_new), device=device, dtype=torch.int64)
+        self.hyp_len = torch.empty((rows,), device=device, dtype=torch.int32)
+        self.hyp_fin = torch.empty((rows,), device=device, dtype=torch.int32)
+        self.unsat = torch.empty((clips,), device=device, dtype=torch.int32)
+        self.beam_idx = torch.empty((rows,), device=device, dtype=torch.int32)
+        self.cand_score = torch.zeros((rows, 2 * K), device=device, dtype=torch.float32)
+        self.cand_tok = torch.zeros((rows, 2 * K), device=device, dtype=torch.int32)
+        self.reset()
+
+    def reset(self):
+        K = self.K
+        self.run_score.fill_(-1.0e9)
+        self.run_score[::K] = 0.0
+        self.hyp_score.fill_(-1.0e9)
+        self.hyp_seq.fill_(self.pad)
+        self.hyp_len.zero_(); self.hyp_fin.zero_()
+        self.unsat.fill_(1)
+        self.beam_idx.copy_(torch.arange(K, dtype=torch.int32).repeat(self.clips))
+
+    def snapshot(self) -> dict:
+        return {f: getattr(self, f).clone() for f in self.FIELDS}
+
+
+def beam_row_topk(logits, bs: BeamState, step_dev, finished, eos_id: int, min_new_tokens: int):
+    """crab_beam_row_topk (csrc/beam.hip): every row's best 2K continuations by run_score + log_softmax(raw logits) into bs.cand_score /
+    bs.cand_tok.  logits [clips * K, V] fp32, unit column stride."""
+    d = _dev(logits)
+    rows, V = logits.shape
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1 or rows != bs.clips * bs.K:
+        raise ValueError(f"logits must be float32 [{bs.clips * bs.K}, V] with unit column stride, got {logits.dtype} {tuple(logits.shape)}")
+    _chk_i32("finished", finished, rows, logits.device)
+    _chk_i32("step_dev", step_dev, 1, logits.device)
+    _lib.check(_lib.load().crab_beam_row_topk(_lib.ctx(d), _stream(), _p(logits), logits.stride(0), rows, V, bs.K, _p(bs.run_score), _p(step_dev),
+                                              _p(finished), int(eos_id), int(min_new_tokens), _p(bs.cand_score), _p(bs.cand_tok)), d)
+
+
+def beam_merge(bs: BeamState, V: int, step_dev, eos_id: int, cur_ids, run_seq, finished):
+    """crab_beam_merge: steps c-g of HF's beam loop on every clip's K x 2K candidates.  run_seq: the decode state's out_ids, int64
+    [rows, max_new]; cur_ids int64 [rows]; finished int32 [rows] receives the clip's done flag."""
+    d = _dev(run_seq)
+    rows = bs.clips * bs.K
+    if run_seq.dtype != torch.int64 or run_seq.dim() != 2 or run_seq.shape[0] != rows or run_seq.shape[1] != bs.max_new or run_seq.stride(1) != 1:
+        raise ValueError(f"run_seq must be int64 [{rows}, {bs.max_new}] with unit column stride, got {run_seq.dtype} {tuple(run_seq.shape)}")
+    if cur_ids.dtype != torch.int64 or cur_ids.dim() != 1 or cur_ids.shape[0] < rows or not cur_ids.is_contiguous() or cur_ids.device != run_seq.device:
+        raise ValueError(f"cur_ids must be a contiguous int64 [{rows}] tensor on {run_seq.device}, got {cur_ids.dtype} {tuple(cur_ids.shape)}")
+    _chk_i32("finished", finished, rows, run_seq.device)
+    _chk_i32("step_dev", step_dev, 1, run_seq.device)
+    _lib.check(_lib.load().crab_beam_merge(_lib.ctx(d), _stream(), _p(bs.cand_score), _p(bs.cand_tok), rows, int(V), bs.K, bs.max_new, _p(step_dev),
+                                           int(eos_id), bs.pad, bs.early, int(bs.length_penalty > 0.0), _p(bs.len_tab), _p(bs.run_score), _p(run_seq),
+                                           run_seq.stride(0), _p(bs.hyp_score), _p(bs.hyp_seq), bs.hyp_seq.stride(0), _p(bs.hyp_len), _p(bs.hyp_fin),
+                                           _p(bs.unsat), _p(cur_ids), _p(bs.beam_idx), _p(finished)), d)
+
+
+def kv_beam_reorder(kc, vc, K: int, beam_idx, finished, pos_dev, first_slot: int = 0):
+    """crab_kv_beam_reorder: the own KV cache [L, rows, Hk, Tmax, d] bf16 x 2 in place, row c K + k <- row c K + beam_idx[c K + k], over the
+    slots first_slot .. pos_dev[0]; clips with an identity beam_idx or finished rows are skipped."""
+    d = _dev(kc)
+    _chk_bf16(kc, vc)
+    if kc.dim() != 5 or kc.shape != vc.shape or not kc.is_contiguous() or not vc.is_contiguous():
+        raise ValueError(f"k / v cache must be contiguous [L, rows, Hk, Tmax, d] tensors of one shape, got {tuple(kc.shape)} and {tuple(vc.shape)}")
+    L, rows, Hk, Tmax, hd = kc.shape
+    _chk_i32("beam_idx", beam_idx, rows, kc.device)
+    _chk_i32("finished", finished, rows, kc.device)
+    _chk_i32("pos_dev", pos_dev, 1, kc.device)
+    _lib.check(_lib.load().crab_kv_beam_reorder(_lib.ctx(d), _stream(), _p(kc), _p(vc), L, rows, int(K), Hk, Tmax, hd, int(first_slot), _p(pos_dev),
+                                                _p(beam_idx), _p(finished)), d)
+
+
 def advance(pos_dev, step_dev):
     d = _dev(pos_dev)
     _lib.check(_lib.load().crab_advance(_lib.ctx(d), _stream(), _p(pos_dev), _p(step_dev)), d)

@@ -290,8 +290,19 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
         the set the step chose from: all but EOS under min_new_tokens, the answer trie's edges in a closed-set call = HF's transition scores
         with normalize_logits=True of a greedy call), .sum_logprob [B], .sum_logprob_allowed [B] and .num_tokens [B] (int32: generated tokens, the
         EOS included).  Entries after a row's EOS are 0.  With do_sample the warpers (temperature, top_k, top_p) enter neither number - they
-        describe the model, not the draw; HF's warped `scores` are not reproduced."""
-        self._check_generate_kwargs(kwargs, self._PROCESSOR_ARGS)
+        describe the model, not the draw; HF's warped `scores` are not reproduced.
+        num_beams > 1: HF beam search (GenerationEngine.generate_beam; csrc/beam.hip) with length_penalty, early_stopping (False | True |
+        "never"), num_return_sequences <= num_beams and min_new_tokens.  Returns the new ids [B * num_return_sequences, n], per clip best
+        hypothesis first, pad_token_id after a hypothesis's EOS; with return_dict_in_generate a GenerateOutput with .sequences and, with
+        output_scores, .sequences_scores [B * num_return_sequences] fp32.  The clip's prompt KV is held once, the beams keep only their own
+        keys.  Refused by name with beams: do_sample, allowed_sequences, repetition_penalty / no_repeat_ngram_size (HF applies them to the
+        log-probs in beam mode, a different edit from the raw-logit one here), several eos ids, output_token_logprobs / output_logits /
+        output_first_logits, both fp8 modes, num_beam_groups / diversity_penalty / constraints.  num_beams = 1 with length_penalty != 1 or
+        num_return_sequences > 1 stays refused."""
+        beams =int(kwargs.get("num_beams") or 1)
+        self._check_generate_kwargs(kwargs, self._PROCESSOR_ARGS | self._BEAM_ARGS if beams > 1 else self._PROCESSOR_ARGS)
+        if beams > 1:
+            return self._generate_beam(batch_input_ids, batch_labels, batch_X_modals, batch_task_names, kwargs)
         sampling = self._sampling(kwargs)
         eos, proc = self._processors(kwargs)
         constraint = self._constraint(kwargs, eos)
@@ -328,6 +339,48 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
                 out.first_logits = res.pop(0)
             return out
         return res
+
+    def _generate_beam(self, batch_input_ids, batch_labels, batch_X_modals, batch_task_names, kwargs):
+        """generate(num_beams > 1): HF beam search through GenerationEngine.generate_beam.  What beam mode does not take is refused by name
+        before any device work."""
+        neutral = {"do_sample": False, "allowed_sequences": None, "allowed_set": None, "repetition_penalty": 1.0, "no_repeat_ngram_size": 0,
+                   "output_token_logprobs": False, "output_logits": False, "output_first_logits": False, "kv_cache_dtype": "bf16", "weight_dtype": "bf16"}
+        for k, off in neutral.items():
+            v = kwargs.get(k)
+            if v is None or v == off or (isinstance(off, bool) and not v):
+                continue
+            raise NotImplementedError(f"generate(num_beams={kwargs['num_beams']}, {k}={v!r}): not implemented in beam mode (plain beam search with "
+                                      "length_penalty, early_stopping, num_return_sequences and min_new_tokens is)")
+        for k in ("kv_cache_dtype", "weight_dtype"):
+            if getattr(self._engine, k, "bf16") != "bf16":
+                raise NotImplementedError(f'generate(num_beams={kwargs["num_beams"]}) on an engine with {k}="{getattr(self._engine, k)}": beam mode is a bf16 path')
+        eos = kwargs.get("eos_token_id", self.config.eos_token_id)
+        if torch.is_tensor(eos):
+            eos = eos.reshape(-1).tolist()
+        if isinstance(eos, (list, tuple)):
+            ids = list(dict.fromkeys(int(e) for e in eos))
+            if len(ids) > 1:
+                raise NotImplementedError(f"generate(num_beams={kwargs['num_beams']}, eos_token_id={ids}): beam mode stops on ONE eos_token_id")
+            eos = ids[0] if ids else None
+        embeds = kwargs.pop("inputs_embeds", None)
+        if embeds is None:
+            inputs = self.prepare_multimodal_inputs(batch_input_ids=batch_input_ids, batch_labels=batch_labels, batch_X_modals=batch_X_modals,
+                                                    return_multi_scale_features=False, return_gt_mask=False, batch_task_names=batch_task_names)
+            embeds = inputs['inputs_embeds']
+        embeds = embeds.to(device=self.device, dtype=BF16)
+        pad = kwargs.get("pad_token_id", self.model.pad_token_id if self.model.pad_token_id is not None else eos)
+        lp = kwargs.get("length_penalty")
+        want_scores = bool(kwargs.get("output_scores")) and bool(kwargs.get("return_dict_in_generate"))
+        res = self._engine.generate_beam(embeds, int(kwargs["num_beams"]), int(kwargs.get("max_new_tokens", 20)), eos_token_id=eos, pad_token_id=pad,
+                                         min_new_tokens=int(kwargs.get("min_new_tokens", 0) or 0), length_penalty=1.0 if lp is None else float(lp),
+                                         early_stopping=kwargs.get("early_stopping") or False,
+                                         num_return_sequences=int(kwargs.get("num_return_sequences") or 1), use_graph=kwargs.get("use_graph", True),
+                                         max_rows=kwargs.get("max_rows"), return_scores=want_scores)
+        if not kwargs.get("return_dict_in_generate"):
+            return res
+        out = type("GenerateOutput", (), {})()
+        out.sequences, out.sequences_scores = res if want_scores else (res, None)
+        return out
 
     @torch.no_grad()
     def generate_batches(self, batches, coalesce: bool = False, max_rows: Optional[int] = None, **kwargs):
@@ -437,6 +490,8 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
 
     # the names of _UNSUPPORTED that the decode step implements (csrc/logits_proc.hip): an entry point that routes them to the engine says so
     _PROCESSOR_ARGS = frozenset(("repetition_penalty", "no_repeat_ngram_size"))
+    # the names of _UNSUPPORTED that generate(num_beams > 1) hands to GenerationEngine.generate_beam (csrc/beam.hip); generate() alone passes them
+    _BEAM_ARGS = frozenset(("num_beams", "length_penalty", "num_return_sequences"))
 
     @classmethod
     def _check_generate_kwargs(cls, kwargs, implemented=frozenset()):

@@ -482,6 +482,50 @@ int crab_logits_edit(crab_ctx* ctx, void* stream, float* logits, int64_t ldl, in
                      const int32_t* stop_ids, int n_stop, int min_new_tokens, int32_t* save_idx, float* save_val, int64_t ld_save);
 int crab_logits_restore(crab_ctx* ctx, void* stream, float* logits, int64_t ldl, int B, int V, const int64_t* cur_ids, int32_t* finished,
                         const int32_t* stop_ids, int n_stop, const int32_t* save_idx, const float* save_val, int64_t ld_save, int n_slots);
+/* Beam search (csrc/beam.hip): the select of a step replaced by HF's vectorised GenerationMixin._beam_search (transformers
+ * generation/utils.py), device-resident and capturable.  The K = num_beams beams of clip c are the decode rows c K .. c K + K - 1
+ * (rows = clips x K); step = step_dev[0].  State of a clip, HF's names in brackets:
+ *     run_score [rows] fp32            [running_beam_scores]   initially (0, -1e9, ..., -1e9) per clip
+ *     run_seq   [rows, ld_run] int64   [running_sequences]     the generated ids only, initially pad_id
+ *     hyp_score [rows] fp32            [beam_scores]           initially -1e9;  sorted, best first
+ *     hyp_seq   [rows, ld_hyp] int64   [sequences]             initially pad_id
+ *     hyp_len   [rows] int32                                   generated tokens of a finished hypothesis (its EOS included), else 0
+ *     hyp_fin   [rows] int32           [is_sent_finished]
+ *     unsat     [clips] int32          [is_early_stop_heuristic_unsatisfied]   initially 1
+ *     finished  [rows] int32           the clip's done flag on each of its rows: !_beam_search_has_unfinished_sequences, per clip
+ * A clip whose rows are finished is FROZEN: none of the three launches changes anything of it (HF keeps stepping it to no effect).
+ * Total order wherever candidates are ranked: the higher score first, then the lower index (flat index k V + token among continuations,
+ * position in the merged list otherwise); torch.topk leaves ties open.  A NaN score ranks as -inf.
+ * crab_beam_row_topk: log_softmax of every row's raw logits (-inf entries are legal), + run_score[row], eos_id at -inf while
+ *     step < min_new_tokens (MinNewTokensLengthLogitsProcessor on the log-probs; eos_id < 0: none), and the row's best 2K candidates,
+ *     sorted, into cand_score / cand_tok [rows, 2K] - replaces log_softmax + the add of utils.py:3388-3420 and the row-local part of
+ *     _get_top_k_continuations (the best 2K of K V lie in the union of the rows' best 2K).
+ * crab_beam_merge: per clip the K x 2K candidates to the best 2K (_get_top_k_continuations), then the stopping criteria (token == eos_id; all
+ *     candidates when step + 1 == max_new), _get_running_beams_for_next_iteration, _update_finished_beams, _check_early_stop_heuristic and
+ *     _beam_search_has_unfinished_sequences.  Writes cur_ids[row] (the next embedding), beam_idx[row] (the parent within the clip, 0 .. K - 1),
+ *     run_seq permuted by parent with the new token in column step, and the state above.  early_stopping: 0 False, 1 True, 2 "never";
+ *     length_penalty_positive: length_penalty > 0 (read by "never" only); len_tab: fp32 [max_new + 1], len_tab[n] = n ** length_penalty
+ *     evaluated in double and rounded once (entry 0 unused) - the device divides (a true fp32 division) and never calls pow.
+ * crab_kv_beam_reorder: the own KV cache [L, rows, Hk, Tmax, head_dim] bf16 x 2 IN PLACE, row c K + k <- row c K + beam_idx[c K + k], over the
+ *     slots first_slot .. pos_dev[0] only - replaces _reorder_cache (utils.py:3477-3489), which index_selects the whole cache.  A clip whose
+ *     beam_idx is the identity or whose rows are finished is skipped.
+ * None reads the host; all are capturable; no atomics.  CRAB_E_INVALID for null operands, rows not a positive multiple of num_beams >= 1,
+ * V < 2 num_beams or > 2^27, max_new < 1, leading dimensions below max_new, an early_stopping outside 0 .. 2, (reorder) first_slot outside
+ * the cache, head_dim not a multiple of 8, caches not 16-byte aligned.  CRAB_E_UNSUPPORTED for num_beams > CRAB_BEAM_MAX, max_new >
+ * CRAB_BEAM_MAX_NEW, (reorder) a cache of 2^31 16-byte units (32 GiB) or more.
+ * ADDED under ABI 13 (crab_abi_version() still returns 13: nothing that existed changed); probe for the symbol, not for a version number. */
+#define CRAB_BEAM_MAX 8
+#define CRAB_BEAM_MAX_NEW 1024   /* max_new_tokens of a beam call */
+int crab_beam_max(void);          /* the values compiled into the library */
+int crab_beam_max_new(void);
+int crab_beam_row_topk(crab_ctx* ctx, void* stream, const float* logits, int64_t ldl, int rows, int V, int num_beams, const float* run_score,
+                       const int32_t* step_dev, const int32_t* finished, int eos_id, int min_new_tokens, float* cand_score, int32_t* cand_tok);
+int crab_beam_merge(crab_ctx* ctx, void* stream, const float* cand_score, const int32_t* cand_tok, int rows, int V, int num_beams, int max_new,
+                    const int32_t* step_dev, int eos_id, int pad_id, int early_stopping, int length_penalty_positive, const float* len_tab,
+                    float* run_score, int64_t* run_seq, int64_t ld_run, float* hyp_score, int64_t* hyp_seq, int64_t ld_hyp, int32_t* hyp_len,
+                    int32_t* hyp_fin, int32_t* unsat, int64_t* cur_ids, int32_t* beam_idx, int32_t* finished);
+int crab_kv_beam_reorder(crab_ctx* ctx, void* stream, void* k_cache, void* v_cache, int L, int rows, int num_beams, int Hk, int Tmax,
+                         int head_dim, int first_slot, const int32_t* pos_dev, const int32_t* beam_idx, const int32_t* finished);
 
 /* ---------------------------------------------------------------------------------------------
  * Teacher-forced scoring (csrc/xent.hip): the language-model loss of models/modeling_llama.py:1261-1274 as reached from
