@@ -1,14 +1,16 @@
 """Differential fuzz of the row kernels around the GEMMs (RMSNorm / LayerNorm on bf16 and fp32 rows, embedding to bf16 / fp32 with skipped and clamped
 ids, row casts and copies, the stand-alone hyper-LoRA router, the SwiGLU pass, arg-max with a suppressed id; r06: the fp32 quantiser, the split-operand GEMM
 and the fp32 GroupNorm of the precise VQGAN encoder) against torch, every output inside
-sentinel guard rows / columns.   python scripts/fuzz_ops.py [cases] [seed]"""
+sentinel guard rows / columns.  Norms, router and SwiGLU: fp64 references on the GPU, every element against the derived bound of
+tests/fuzz_bounds.py (one bf16 rounding + a derived fp32 term, no constant).   python scripts/fuzz_ops.py [cases] [seed]"""
 import os, random, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-import torch.nn.functional as F
 from crab_amd import ops, _lib
+from tests import fuzz_bounds as FB
 
 BF = torch.bfloat16
+run = FB.Run()                                                      # norms, router, SwiGLU: fp64 references, every element against its derived bound
 NCASE = int(sys.argv[1]) if len(sys.argv) > 1 else 400
 rng = random.Random(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
 bad, rejected, done, why = [], 0, 0, {}
@@ -41,14 +43,14 @@ for case in range(NCASE):
             eps = rng.choice([1e-5, 1e-6, 1e-12])
             buf, out = guarded(M, D, BF, gap)
             desc += f" D={D} in={'fp32' if f32 else 'bf16'} gap={gap} eps={eps}"
-            xf = x.float()
+            # fp64 reference and per-element bound from tests/fuzz_bounds.py (a bf16 row: x_hat is rounded before the weight, as the kernel does)
             if kind == "rmsnorm":
                 ops.rmsnorm(x, w, eps, out=out)
-                ref = xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps) * w.float()
+                ref, bound = FB.rmsnorm_bound(x, w, eps, round_xhat=not f32)
             else:
                 ops.layernorm(x, w, b, eps, out=out)
-                ref = F.layer_norm(xf, (D,), w.float(), b.float() if b is not None else None, eps)
-            err, tol = float((out.float() - ref).abs().max()) / (float(ref.abs().max()) + 1e-9), 1.2e-2
+                ref, bound = FB.layernorm_bound(x, w, b, eps)
+            run.judge(bad, desc, kind, out, ref, bound)
             ok_guard = intact(buf, D)
         elif kind == "embedding":
             V, D = rng.choice([10, 320, 32017]), rng.choice([8, 128, 4096])
@@ -81,23 +83,18 @@ for case in range(NCASE):
             ra = (torch.randn((rows + 15) // 16 * 16, K, device="cuda", generator=g) * K ** -0.5).to(BF)
             buf, u = guarded(M, ucols, BF, 8)
             ops.hyperlora_route(x, ra, nproj, nl, r, ucols, 2.0, out=u)
-            t = x.float() @ ra.float().t()
-            ref = torch.zeros(M, ucols, device="cuda")
-            for p in range(nproj):
-                tt = t[:, p * (nl + r):(p + 1) * (nl + r)]
-                pr = torch.softmax(tt[:, :nl], -1)
-                ref[:, p * nl * r:(p + 1) * nl * r] = (2.0 * pr[:, :, None] * tt[:, None, nl:]).reshape(M, nl * r)
-            err, tol = float((u.float() - ref).abs().max()) / (float(ref.abs().max()) + 1e-9), 1.5e-2
             desc += f" K={K} nproj={nproj} nl={nl} r={r} ucols={ucols}"
+            ref, bound = FB.route_bound(x, ra, nproj, nl, r, ucols, 2.0)
+            run.judge(bad, desc, kind, u, ref, bound)
             ok_guard = intact(buf, ucols)
         elif kind == "swiglu":
             I = rng.choice([4, 64, 1376, 11008])
             gu = torch.randn(M, 2 * I + gap, device="cuda", generator=g).to(BF)[:, :2 * I]
             buf, out = guarded(M, I, BF, gap)
             ops.swiglu(gu, out=out)
-            ref = F.silu(gu[:, :I].float()) * gu[:, I:].float()
-            err, tol = float((out.float() - ref).abs().max()) / (float(ref.abs().max()) + 1e-9), 1.0e-2
             desc += f" I={I}"
+            ref, bound = FB.swiglu_bound(gu)
+            run.judge(bad, desc, kind, out, ref, bound)
             ok_guard = intact(buf, I)
         elif kind == "vq_nearest":
             # r06: the fp32 quantiser (crab_vq_nearest_f32) against torch's fp32 expression of quantize.py:286-290; ids equal wherever the top-2 gap is above fp32 noise
@@ -168,7 +165,7 @@ for case in range(NCASE):
     done += 1
     if not (err <= tol): bad.append(desc + f" -> err {err:.3e} (tol {tol})")
     if not ok_guard: bad.append(desc + " -> a store landed outside the output block")
-print(f"{done} cases computed, {rejected} rejected by the library, {len(bad)} failures")
 for k_, v_ in sorted(why.items(), key=lambda kv: -kv[1]): print(f"  rejected x{v_}: {k_}")
 for b_ in bad[:40]: print("FAIL", b_)
+print(f"{done} cases computed, {rejected} rejected by the library, {len(bad)} failures; norms / router / SwiGLU: {run}")
 sys.exit(1 if bad else 0)

@@ -1,7 +1,7 @@
 """Differential fuzz through the C-ABI at random shapes around every dispatch boundary - short fixed-seed runs of the twelve generators under scripts/
 (one process: scripts/fuzz_all.py; the cases are the same on every run):
-  fuzz_gemm.py           the GEMM regimes x epilogues against fp32 torch on the same bf16 operands,
-  fuzz_attn.py           the attention entry points x masks,
+  fuzz_gemm.py           the GEMM regimes x epilogues against an fp64 product of the same bf16 operands,
+  fuzz_attn.py           the attention entry points x masks against fp64 attention,
   fuzz_decoder.py        the whole decoder path on random tiny Llama / Qwen2 configurations (GQA, adapter ranks, batch 1 .. 260, both layer sequencers,
                          graph and eager; the EOS / min_new_tokens state machine; forward() under random 2-D masks) against the fp32 CPU oracle,
   fuzz_multimodal.py     prepare_multimodal_inputs on random tiny encoder stacks against the oracle - both bounded by the oracle's own bf16-storage
@@ -18,6 +18,8 @@
                          every residue modulo 64, spread row scales, all forms of the slot argument, every documented refusal; one decode step of the
                          stack on a CPU-built cache against the oracle; generate() / generate_many() cache contents equal to the quantised bf16 cache
                          under every prefill chunking; call sequences that mix the two modes (tests/test_kv_fp8_host.py pins the coverage of its cases).
+Verdict of fuzz_gemm / fuzz_attn / fuzz_ops (norms, router, SwiGLU) / fuzz_rope_epilogue (rows > 256): fp64 references, EVERY output element within
+the bound tests/fuzz_bounds.py derives for it (one bf16 rounding + the kernel's fp32 terms); no tolerance constant in a fuzzer (tests/test_fuzz_bounds_host.py).
 (r05: half the r04 case count here - the suite has a time limit; tests/test_slow_gpu.py runs 8x that (scale 4) under `-m gpu_slow`.)
 A combination outside a stated limit must be REJECTED (CRAB_E_INVALID / CRAB_E_UNSUPPORTED), never computed wrong; outputs sit inside sentinel guards."""
 import os
