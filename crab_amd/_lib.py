@@ -217,6 +217,8 @@ SYMBOLS = {
     "crab_beam_merge": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
                              _vp, _vp]),
     "crab_kv_beam_reorder": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "crab_cfg_mix": (_i, [_vp, _vp, _vp, _i64, _i, _i, _f, _vp, _vp, _i64]),
+    "crab_cfg_follow": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _vp, _i]),
     "crab_lm_head_xent_workspace": (_i64, [_i, _i]),
     "crab_lm_head_xent": (_i, [_vp, _vp, _vp, _i64, _vp, _i, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _i64]),
     "crab_xent_reduce": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),

@@ -1090,7 +1090,8 @@ class GenerationEngine:
         between the two (ops.logits_edit) and written back right after the select (ops.logits_restore, which also marks a row that emitted a
         further stop id as finished): the select chooses from the edited row, everything else - the logits a caller gets, both log-probability
         planes - sees the raw one.
-        A state with st.beam (generate_beam) takes none of these: its select is the beam step (csrc/beam.hip)."""
+        A state with st.beam (generate_beam) takes none of these: its select is the beam step (csrc/beam.hip).
+        A state with st.cfg (generate_guided) takes none of these either: the select runs on the guided scores of its pairs (csrc/cfg.hip)."""
         if st.beam is not None:
             # beam search (generate_beam): the select is the beam step - the rows' best 2K continuations, the clip's merge (HF's steps c-g), then
             # the own cache rows follow their parents; `finished` carries the clip's done flag, so the EOS check of _run_steps works unchanged
@@ -1098,6 +1099,16 @@ class GenerationEngine:
             ops.beam_row_topk(st.logits, bs, st.step_dev, st.finished, st.eos, st.min_new)
             ops.beam_merge(bs, st.logits.shape[1], st.step_dev, st.eos, st.cur_ids, st.out_ids, st.finished)
             ops.kv_beam_reorder(st.kc, st.vc, bs.K, bs.beam_idx, st.finished, st.pos_dev)
+            return
+        if st.cfg is not None:
+            # classifier-free guidance (generate_guided; csrc/cfg.hip): rows 0 .. B - 1 are the conditional prompts, rows B .. 2B - 1 their
+            # unconditional ones.  The guided scores of the pairs go to st.guided (the raw logits stay what the lm_head wrote), the ordinary
+            # select runs on those B rows - a sampled row's stream is keyed by the clip's row index - and the unconditional rows take their
+            # pair's token, so both embed it at the next step
+            scale, Bc = st.cfg
+            ops.cfg_mix(st.logits, st.guided, Bc, scale, st.finished)
+            self._select_token(st, st.guided)
+            ops.cfg_follow(st.cur_ids, st.out_ids, st.finished, st.step_dev, Bc)
             return
         if st.lp is not None:
             tr = st.trie
@@ -1112,19 +1123,23 @@ class GenerationEngine:
         if st.lp is not None:
             ops.logprob_gather(st.logits, st.cur_ids, st.step_dev, st.lp_norm, st.lp)
 
-    def _select_token(self, st: "_DecodeState"):
+    def _select_token(self, st: "_DecodeState", logits=None):
+        """logits: the scores to choose from when they are not st.logits - a guided state's st.guided, whose B rows are the FIRST rows of the
+        state: the select then writes those rows' words."""
+        logits = st.logits if logits is None else logits
         if st.trie is not None:
             t, k, p_, seed = st.sampling if st.sampling is not None else (0.0, 0, 1.0, 0)
-            ops.constrained_select(st.logits, st.trie.edge_off, st.trie.edge_tok, st.trie.edge_dst, st.node, st.cur_ids, st.out_ids, st.step_dev,
+            ops.constrained_select(logits, st.trie.edge_off, st.trie.edge_tok, st.trie.edge_dst, st.node, st.cur_ids, st.out_ids, st.step_dev,
                                    st.finished, st.eos, st.pad, st.min_new, t, k, p_, seed + 7919 * st.slot)
         elif st.sampling is None:
-            ops.greedy_select(st.logits, st.cur_ids, st.out_ids, st.step_dev, st.finished, st.eos, st.pad, st.min_new)
+            ops.greedy_select(logits, st.cur_ids, st.out_ids, st.step_dev, st.finished, st.eos, st.pad, st.min_new)
         else:
             t, k, p_, seed = st.sampling
-            ops.sample_select(st.logits, st.cur_ids, st.out_ids, st.step_dev, st.finished, st.eos, st.pad, st.min_new, t, k, p_, seed + 7919 * st.slot)
+            ops.sample_select(logits, st.cur_ids, st.out_ids, st.step_dev, st.finished, st.eos, st.pad, st.min_new, t, k, p_, seed + 7919 * st.slot)
 
     def _state(self, B: int, S: int, max_new_tokens: int, eos_token_id, pad_token_id, min_new_tokens: int, return_hidden: bool, slot: int,
-               sampling=None, ragged: bool = False, extra_key=(), constraint=None, logprobs: bool = False, processors=None) -> "_DecodeState":
+               sampling=None, ragged: bool = False, extra_key=(), constraint=None, logprobs: bool = False, processors=None,
+               cfg=None) -> "_DecodeState":
         """The persistent decode state of `slot` for B sequences whose (longest) prompt has S rows: KV cache, per-row words, logits and the HIP
         graph captured over them.  Kept per slot and reused by every call whose shapes, flags and buffers are the same: the key holds
         everything the captured launches bake in (pointers included).  ragged: the state of a coalesced batch (generate_many(coalesce=True)) -
@@ -1135,7 +1150,11 @@ class GenerationEngine:
         whole vocabulary, plane 1: within the allowed set; zeroed by every call like out_ids) and st.lp_norm [B, 4], and _select fills them;
         the flag is part of the key, so a graph captured without the two launches is never replayed for a call that wants them.
         processors: (repetition_penalty, no_repeat_ngram_size, stop_token_ids) or None - a non-neutral triple owns st.save_idx / st.save_val
-        (the save area of crab_logits_edit / crab_logits_restore) and st.stop_dev, and its values enter the key in the same way."""
+        (the save area of crab_logits_edit / crab_logits_restore) and st.stop_dev, and its values enter the key in the same way.
+        cfg: (guidance_scale, pairs) or None - classifier-free guidance (generate_guided): the B = 2 * pairs rows are the conditional rows and
+        then their unconditional ones, the state owns st.guided [pairs, V] fp32 (the scores the select reads, crab_cfg_mix) and _select
+        takes the guided route.  The scale is baked into the captured launch, so both values enter the key; st.guided is born with the
+        state and dies with it."""
         if int(max_new_tokens) < 1:                             # HF: GenerationConfig.validate() - "`max_new_tokens` must be greater than 0"; here the first token's slot would not exist
             raise ValueError(f"`max_new_tokens` must be greater than 0, but is {max_new_tokens}.")
         dev = self.device
@@ -1172,7 +1191,8 @@ class GenerationEngine:
                self.model.layers[0].self_attn._qkv.W.data_ptr(),
                self.model.layers[0].self_attn._qkv.RA is not None, sampling, bool(ragged),
                self._kv_mode, ks.data_ptr() if ks is not None else 0, vs.data_ptr() if vs is not None else 0, w8_key, bool(logprobs)) + tuple(extra_key) + \
-            (constraint.dev.key if constraint is not None else ()) + (("proc",) + proc if proc is not None else ())
+            (constraint.dev.key if constraint is not None else ()) + (("proc",) + proc if proc is not None else ()) + \
+            (("cfg", float(cfg[0]), int(cfg[1])) if cfg is not None else ())
         st = self._dec.get(slot)
         if st is None or st.key != key:
             st = _DecodeState()
@@ -1203,6 +1223,8 @@ class GenerationEngine:
             st.save_idx = torch.full((B, n_slots), -1, device=dev, dtype=torch.int32) if proc is not None else None
             st.save_val = torch.zeros((B, n_slots), device=dev, dtype=torch.float32) if proc is not None else None
             st.stop_dev = torch.tensor(stops, dtype=torch.int32).to(dev) if stops else None
+            st.cfg = (float(cfg[0]), int(cfg[1])) if cfg is not None else None
+            st.guided = torch.empty((int(cfg[1]), V), device=dev, dtype=torch.float32) if cfg is not None else None
             self._dec[slot] = st
         st.S = S
         st.cur_ids.zero_(); st.out_ids.fill_(pad_token_id if pad_token_id is not None else 0); st.finished.zero_()
@@ -1279,7 +1301,8 @@ class GenerationEngine:
             g = g1 + 1
 
     def _start_ragged(self, embeds_list: List[torch.Tensor], max_new_tokens: int, eos_token_id, pad_token_id, min_new_tokens: int,
-                      sink=None, sampling=None, return_hidden: bool = False, constraint=None, logprobs: bool = False, processors=None) -> "_DecodeState":
+                      sink=None, sampling=None, return_hidden: bool = False, constraint=None, logprobs: bool = False, processors=None,
+                      cfg=None) -> "_DecodeState":
         """The decode state of SEVERAL generate() calls coalesced into one batch.  Group g = [B_g, S_g, D] is one call of the eval loop: its
         own prompt length and left padding, positions 0 .. S_g - 1 (unified_llama.py:262-267).  All rows share one KV cache [L, sum B_g, Hk,
         Tmax, d] in which every group is RIGHT-ALIGNED at Smax = max S_g: group g's prompt occupies slots Smax - S_g .. Smax - 1, so the token
@@ -1292,7 +1315,7 @@ class GenerationEngine:
         Ss = [int(e.shape[1]) for e in embeds_list]
         Bt, Smax = sum(Bs), max(Ss)
         st = self._state(Bt, Smax, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, return_hidden, 0, sampling, ragged=True,
-                         constraint=constraint, logprobs=logprobs, processors=processors)
+                         constraint=constraint, logprobs=logprobs, processors=processors, cfg=cfg)
         st.row_off.copy_(torch.tensor([Smax - S for B, S in zip(Bs, Ss) for _ in range(B)], dtype=torch.int32), non_blocking=False)
         waste = sum(B * (Smax - S) for B, S in zip(Bs, Ss)) / max(1, sum(B * S for B, S in zip(Bs, Ss)))
         if len(set(Ss)) > 1 and waste <= RAGGED_PAD_MAX:
@@ -1646,6 +1669,115 @@ class GenerationEngine:
             outs.append(r if len(r) > 1 else out)
             r0 = r1
         return outs
+
+    # ------------------------------------------------------------------ classifier-free guidance: a clip's two prompts as two rows of one wave
+    @torch.no_grad()
+    def generate_guided(self, embeds: torch.Tensor, negative_embeds: torch.Tensor, guidance_scale: float, max_new_tokens: int,
+                        eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, min_new_tokens: int = 0, use_graph: bool = True,
+                        sampling=None, return_step_logits: bool = False, kv_cache_dtype: Optional[str] = None, weight_dtype: Optional[str] = None,
+                        max_rows: Optional[int] = None, **refused):
+        """Classifier-free guidance (HF's UnbatchedClassifierFreeGuidanceLogitsProcessor; with a negative prompt that is the question without
+        its clip, "visual contrastive decoding"): embeds [B, S, D] are the conditional prompts, negative_embeds [B, Sn, D] the unconditional
+        ones, and every token is chosen from
+            lu + guidance_scale * (lc - lu),    lc / lu = log_softmax of the conditional / unconditional logits,
+        greedy or, with sampling = (temperature, top_k, top_p, seed), in HF's sample mode (the guided scores go through the warpers, HF's
+        order).  HF runs a second model forward per step from a Python callback; here the two prompts of a clip are two ROWS of one ragged
+        wave (_start_ragged: conditional rows first, unconditional rows after, each group with its own length, right-aligned in one KV cache),
+        so the weights stream once per step for both and the step stays one captured graph: crab_cfg_mix -> the ordinary select on the B
+        guided rows -> crab_cfg_follow (csrc/cfg.hip), which hands the unconditional row its pair's token.  An 800-row clip prompt beside a
+        30-row text prompt takes the per-group prefill form by the RAGGED_PAD_MAX rule.
+        A wave holds at most min(max_rows, ops.DECODE_MAX_ROWS) // 2 clips and as many as the memory plan admits; more clips run as
+        successive waves of about equal size, a pair is never split (sample mode then draws per (seed, step, row of the wave)).
+        Returns the NEW ids of the conditional rows [B, n], trimmed like generate() trims them; with return_step_logits also the RAW step
+        logits [2B, n, V] fp32 (conditional rows, then unconditional rows): what the lm_head wrote, not the guided scores.
+        Deviation from HF: a token whose logit is -inf in either row scores -inf (HF: NaN where both are).
+        Refused by name before any device work: constraint, return_logprobs, processors, return_hidden, return_first_logits,
+        decode_streams > 1, several eos ids, guidance_scale <= 1 (HF treats 1 as off: that is the caller's plain generate())."""
+        for name, v in refused.items():
+            if name not in ("constraint", "return_logprobs", "processors", "return_hidden", "return_first_logits", "decode_streams"):
+                raise TypeError(f"generate_guided() got an unexpected keyword argument {name!r}")
+            if name == "decode_streams":
+                if v is not None and int(v) > 1:
+                    raise NotImplementedError(f"generate_guided(decode_streams={v}): a guided wave is one decode state (a pair's rows step together)")
+            elif name == "processors":
+                if normalize_processors(v) is not None:
+                    raise NotImplementedError("generate_guided(processors=...): not implemented with guidance (the edits would have to be applied to the guided scores)")
+            elif v is not None and v is not False:
+                raise NotImplementedError(f"generate_guided({name}=...): not implemented with guidance")
+        g = float(guidance_scale)
+        if not g > 1.0:
+            raise NotImplementedError(f"guidance_scale = {guidance_scale}: guidance needs a scale > 1 (HF treats 1 as off - call generate())")
+        if embeds.dim() != 3 or negative_embeds.dim() != 3 or embeds.shape[2] != negative_embeds.shape[2]:
+            raise ValueError(f"generate_guided: embeds [B, S, D] and negative_embeds [B, Sn, D] expected, got {tuple(embeds.shape)} and "
+                             f"{tuple(negative_embeds.shape)}")
+        if embeds.shape[0] != negative_embeds.shape[0] or embeds.shape[0] < 1:
+            raise ValueError(f"generate_guided: {embeds.shape[0]} prompts and {negative_embeds.shape[0]} negative prompts - one negative prompt per row")
+        if isinstance(eos_token_id, (list, tuple)):
+            if len(set(int(e) for e in eos_token_id)) > 1:
+                raise NotImplementedError(f"eos_token_id = {list(eos_token_id)}: a guided call stops on ONE id")
+            eos_token_id = eos_token_id[0] if len(eos_token_id) else None
+        if int(max_new_tokens) < 1:
+            raise ValueError(f"`max_new_tokens` must be greater than 0, but is {max_new_tokens}.")
+        cap = (min(int(max_rows), ops.DECODE_MAX_ROWS) if max_rows else ops.DECODE_MAX_ROWS) // 2
+        if cap < 1:
+            raise ValueError(f"max_rows = {max_rows}: a pair needs two rows")
+        return self._call(kv_cache_dtype, weight_dtype, self._generate_guided, embeds, negative_embeds, g, int(max_new_tokens), eos_token_id,
+                          pad_token_id, int(min_new_tokens), use_graph, sampling, return_step_logits, cap)
+
+    def _generate_guided(self, embeds, negative_embeds, scale, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling,
+                         return_step_logits, cap):
+        """Plan the waves - whole pairs, at most `cap` per wave and what the device's memory holds - run them, join them as _generate_split
+        joins the groups of a split batch (a wave that stopped early is padded with pad ids / zero logits)."""
+        embeds = embeds.to(device=self.device, dtype=BF16)
+        negative_embeds = negative_embeds.to(device=self.device, dtype=BF16)
+        B = int(embeds.shape[0])
+        Smax = max(int(embeds.shape[1]), int(negative_embeds.shape[1]))
+        per = 2 * self.bytes_per_sequence(Smax, max_new_tokens) + self.lm_head.weight.shape[0] * 4       # both rows sit in one cache of Smax rows; + the guided row
+        budget = self.memory_budget(0, 0, slots=1)
+        fit = (int(0.94 * budget) - self.fixed_bytes(2 * min(B, cap), Smax)) // per
+        n_waves = -(-B // max(1, min(cap, fit)))
+        sizes = [B // n_waves + (1 if i < B % n_waves else 0) for i in range(n_waves)]
+        plan = {"B": B, "groups": sizes, "bytes_per_seq": per, "budget": budget, "guided": True}
+        pad = int(pad_token_id) if pad_token_id is not None else (int(eos_token_id) if eos_token_id is not None else 0)
+        ids, cond, unc, b0 = [], [], [], 0
+        for n in sizes:
+            smp = None if sampling is None else (sampling[0], sampling[1], sampling[2], sampling[3] + 104729 * b0)
+            out, sl = self._guided_wave(embeds[b0:b0 + n], negative_embeds[b0:b0 + n], scale, max_new_tokens, eos_token_id, pad_token_id,
+                                        min_new_tokens, use_graph, smp, return_step_logits)
+            ids.append(out)
+            if return_step_logits:
+                cond.append(sl[:n]); unc.append(sl[n:])
+            b0 += n
+        self.last_plan = plan
+        n_max = max(t.shape[1] for t in ids)
+
+        def widen(t, fill):
+            if t.shape[1] == n_max:
+                return t
+            return torch.cat([t, torch.full((t.shape[0], n_max - t.shape[1]) + tuple(t.shape[2:]), fill, device=t.device, dtype=t.dtype)], 1)
+
+        out = ids[0] if n_waves == 1 else torch.cat([widen(t, pad) for t in ids], 0)
+        if not return_step_logits:
+            return out
+        return out, torch.cat([widen(t, 0) for t in cond + unc], 0)
+
+    def _guided_wave(self, embeds, negative_embeds, scale, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling,
+                     return_step_logits):
+        """One wave of whole pairs: a ragged state of two groups.  Returns fresh (ids of the conditional rows [B, n], raw step logits
+        [2B, n, V] or None)."""
+        B = int(embeds.shape[0])
+        steps = []
+
+        def sink(st):
+            if return_step_logits:
+                steps.append(st.logits.clone())
+
+        with _ws_slot(0):
+            st = self._start_ragged([embeds, negative_embeds], max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, sink, sampling,
+                                    cfg=(scale, B))
+        self._run_steps([st], max_new_tokens, use_graph and max_new_tokens > 2, False, True, sink if return_step_logits else None)
+        out = _trim_at_eos(st.out_ids[:B], int(st.step_dev.item()), st.eos_all).clone()
+        return out, (torch.stack(steps, 1)[:, : out.shape[1]] if return_step_logits else None)
 
     # ------------------------------------------------------------------ several questions per clip on one prefix KV
     def shared_prefix_bytes(self, C: int, P: int, B: int, S: int, max_new_tokens: int) -> int:

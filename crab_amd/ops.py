@@ -744,6 +744,44 @@ def logprob_gather(logits, cur_ids, step_dev, norm, lp):
                                                _p(lp), lp.stride(1), lp.stride(0), int(lp.shape[2])), d)
 
 
+def cfg_mix(logits, guided, B: int, scale: float, finished):
+    """crab_cfg_mix (csrc/cfg.hip), BEFORE the select of a guided decode step: pair b < B is row b (conditional) and row B + b (unconditional)
+    of logits [2B, V] fp32; guided[b] = lu + scale * (lc - lu) over the two rows' log-softmax - fp32 [B, V], a buffer of its own (the logits
+    are never written).  Row stride >= V on both; finished int32 [>= B] (a finished pair is computed like any other)."""
+    d = _dev(logits)
+    B = int(B)
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[0] != 2 * B or B < 1 or \
+            logits.stride(0) < logits.shape[1]:
+        raise ValueError(f"logits must be float32 [{2 * B}, V] rows (conditional rows first) with unit column stride and a row stride >= V, got "
+                         f"{logits.dtype} {tuple(logits.shape)} strides {logits.stride()}")
+    V = int(logits.shape[1])
+    if guided.dtype != torch.float32 or tuple(guided.shape) != (B, V) or guided.stride(1) != 1 or guided.stride(0) < V or guided.device != logits.device:
+        raise ValueError(f"guided must be a float32 [{B}, {V}] tensor with unit column stride and a row stride >= {V} on {logits.device}, got "
+                         f"{guided.dtype} {tuple(guided.shape)} strides {guided.stride()} on {guided.device}")
+    _chk_i32("finished", finished, B, logits.device)
+    _lib.check(_lib.load().crab_cfg_mix(_lib.ctx(d), _stream(), _p(logits), logits.stride(0), B, V, float(scale), _p(finished), _p(guided),
+                                        guided.stride(0)), d)
+
+
+def cfg_follow(cur_ids, out_ids, finished, step_dev, B: int):
+    """crab_cfg_follow, AFTER the select of a guided decode step and before advance: the unconditional row B + b takes cur_ids[b],
+    out_ids[b, step_dev[0]] and finished[b] of its pair; nothing when the step is past out_ids' last column.  cur_ids int64 [2B], out_ids
+    int64 [2B, n_steps] with unit column stride, finished int32 [2B]."""
+    d = _dev(cur_ids)
+    B = int(B)
+    dev = cur_ids.device
+    if B < 1 or cur_ids.dtype != torch.int64 or cur_ids.dim() != 1 or cur_ids.shape[0] < 2 * B or not cur_ids.is_contiguous():
+        raise ValueError(f"cur_ids must be a contiguous int64 [{2 * B}] tensor, got {cur_ids.dtype} {tuple(cur_ids.shape)}")
+    if out_ids.dtype != torch.int64 or out_ids.dim() != 2 or out_ids.shape[0] < 2 * B or out_ids.shape[1] < 1 or out_ids.stride(1) != 1 or \
+            out_ids.stride(0) < out_ids.shape[1] or out_ids.device != dev:
+        raise ValueError(f"out_ids must be an int64 [{2 * B}, n_steps] tensor with unit column stride on {dev}, got {out_ids.dtype} "
+                         f"{tuple(out_ids.shape)} on {out_ids.device}")
+    _chk_i32("finished", finished, 2 * B, dev)
+    _chk_i32("step_dev", step_dev, 1, dev)
+    _lib.check(_lib.load().crab_cfg_follow(_lib.ctx(d), _stream(), _p(cur_ids), _p(out_ids), out_ids.stride(0), int(out_ids.shape[1]), _p(finished),
+                                           _p(step_dev), B), d)
+
+
 LOGITS_PROC_MAX_STOP = 8            # stop ids beyond eos_token_id that crab_logits_edit / crab_logits_restore take
 LOGITS_PROC_MAX_STEPS = 8192        # history tokens crab_logits_edit holds in LDS
 

@@ -298,9 +298,21 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
         keys.  Refused by name with beams: do_sample, allowed_sequences, repetition_penalty / no_repeat_ngram_size (HF applies them to the
         log-probs in beam mode, a different edit from the raw-logit one here), several eos ids, output_token_logprobs / output_logits /
         output_first_logits, both fp8 modes, num_beam_groups / diversity_penalty / constraints.  num_beams = 1 with length_penalty != 1 or
-        num_return_sequences > 1 stays refused."""
+        num_return_sequences > 1 stays refused.
+        guidance_scale > 1: classifier-free guidance (HF's UnbatchedClassifierFreeGuidanceLogitsProcessor; GenerationEngine.generate_guided,
+        csrc/cfg.hip) against the unconditional prompt negative_inputs_embeds [B, Sn, D] or negative_inputs (a dict of the four generate()
+        arguments, e.g. the question without its clip: visual contrastive decoding) - one of the two is required.  Both prompts of a row
+        decode as two rows of one ragged batch, every token is chosen from lu + guidance_scale * (lc - lu) over the two log-softmaxes; greedy
+        and do_sample, min_new_tokens, one eos_token_id, both fp8 modes, max_rows.  output_logits + return_dict_in_generate gives the RAW
+        logits of the conditional rows.  None and 1 are off.  Refused by name with guidance: num_beams > 1, allowed_sequences,
+        output_token_logprobs, output_first_logits, repetition_penalty, no_repeat_ngram_size, several eos ids, decode_streams > 1, a scale
+        below 1.  A token that is -inf in either row scores -inf (HF: NaN where both are)."""
         beams =int(kwargs.get("num_beams") or 1)
-        self._check_generate_kwargs(kwargs, self._PROCESSOR_ARGS | self._BEAM_ARGS if beams > 1 else self._PROCESSOR_ARGS)
+        # _GUIDANCE_ARGS is read from the class: generate() alone routes guidance_scale, whatever object stands in for self
+        self._check_generate_kwargs(kwargs, (self._PROCESSOR_ARGS | self._BEAM_ARGS if beams > 1 else self._PROCESSOR_ARGS) | UnifiedForCausalLM._GUIDANCE_ARGS)
+        scale = kwargs.get("guidance_scale")
+        if scale is not None and float(scale) != 1.0:          # None and 1 are off (HF adds its processor under the same condition): the plain call below
+            return UnifiedForCausalLM._generate_guided(self, batch_input_ids, batch_labels, batch_X_modals, batch_task_names, kwargs)
         if beams > 1:
             return self._generate_beam(batch_input_ids, batch_labels, batch_X_modals, batch_task_names, kwargs)
         sampling = self._sampling(kwargs)
@@ -339,6 +351,59 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
                 out.first_logits = res.pop(0)
             return out
         return res
+
+    def _generate_guided(self, batch_input_ids, batch_labels, batch_X_modals, batch_task_names, kwargs):
+        """generate(guidance_scale = g): classifier-free guidance through GenerationEngine.generate_guided.  The negative (unconditional) prompt
+        comes as negative_inputs_embeds [B, Sn, D] or as negative_inputs = a dict of the four generate() arguments, which goes through
+        prepare_multimodal_inputs like the prompt itself (the question without its clip: visual contrastive decoding).  HF's default - the last
+        prompt token alone - has no meaning when the prompt is inputs_embeds, so a missing negative prompt is an error.  What guidance does
+        not combine with is refused by name before any device work."""
+        scale = float(kwargs["guidance_scale"])
+        neutral = {"num_beams": 1, "allowed_sequences": None, "allowed_set": None, "output_token_logprobs": False, "output_first_logits": False,
+                   "repetition_penalty": 1.0, "no_repeat_ngram_size": 0}
+        for k, off in neutral.items():
+            v = kwargs.get(k)
+            if v is None or v == off or (isinstance(off, bool) and not v):
+                continue
+            raise NotImplementedError(f"generate(guidance_scale={scale}, {k}={v!r}): not implemented with guidance (greedy and do_sample with "
+                                      "min_new_tokens, one eos_token_id, output_logits and both fp8 modes are)")
+        eos = kwargs.get("eos_token_id", self.config.eos_token_id)
+        if torch.is_tensor(eos):
+            eos = eos.reshape(-1).tolist()
+        if isinstance(eos, (list, tuple)):
+            ids = list(dict.fromkeys(int(e) for e in eos))
+            if len(ids) > 1:
+                raise NotImplementedError(f"generate(guidance_scale={scale}, eos_token_id={ids}): a guided call stops on ONE eos_token_id")
+            eos = ids[0] if ids else None
+        neg, neg_inputs = kwargs.pop("negative_inputs_embeds", None), kwargs.pop("negative_inputs", None)
+        if (neg is None) == (neg_inputs is None):
+            raise ValueError(f"generate(guidance_scale={scale}) needs the unconditional prompt: negative_inputs_embeds [B, Sn, D] or negative_inputs "
+                             "(a dict of batch_input_ids, batch_labels, batch_X_modals, batch_task_names), one of the two - HF's default, the "
+                             "last prompt token, has no meaning with inputs_embeds")
+        sampling = UnifiedForCausalLM._sampling(kwargs)
+        embeds = kwargs.pop("inputs_embeds", None)
+        prep = lambda d: self.prepare_multimodal_inputs(batch_input_ids=d["batch_input_ids"], batch_labels=d.get("batch_labels"),
+                                                        batch_X_modals=d.get("batch_X_modals"), return_multi_scale_features=False,
+                                                        return_gt_mask=False, batch_task_names=d.get("batch_task_names"))['inputs_embeds']
+        if embeds is None:
+            embeds = prep(dict(batch_input_ids=batch_input_ids, batch_labels=batch_labels, batch_X_modals=batch_X_modals, batch_task_names=batch_task_names))
+        if neg is None:
+            neg = prep(neg_inputs)
+        embeds, neg = embeds.to(device=self.device, dtype=BF16), neg.to(device=self.device, dtype=BF16)
+        pad = kwargs.get("pad_token_id", self.model.pad_token_id if self.model.pad_token_id is not None else eos)
+        want_logits = bool(kwargs.get("output_logits")) and bool(kwargs.get("return_dict_in_generate"))
+        res = self._engine.generate_guided(embeds, neg, scale, int(kwargs.get("max_new_tokens", 20)), eos_token_id=eos, pad_token_id=pad,
+                                           min_new_tokens=int(kwargs.get("min_new_tokens", 0) or 0), use_graph=kwargs.get("use_graph", True),
+                                           sampling=sampling, return_step_logits=want_logits, kv_cache_dtype=kwargs.get("kv_cache_dtype"),
+                                           weight_dtype=kwargs.get("weight_dtype"), max_rows=kwargs.get("max_rows"),
+                                           decode_streams=int(kwargs.get("decode_streams", 1)))
+        if not want_logits:
+            return res
+        out = type("GenerateOutput", (), {})()
+        out.sequences, sl = res
+        sl = sl[: out.sequences.shape[0]]                      # the raw logits of the conditional rows
+        out.logits = tuple(sl[:, i] for i in range(sl.shape[1]))
+        return out
 
     def _generate_beam(self, batch_input_ids, batch_labels, batch_X_modals, batch_task_names, kwargs):
         """generate(num_beams > 1): HF beam search through GenerationEngine.generate_beam.  What beam mode does not take is refused by name
@@ -492,6 +557,8 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
     _PROCESSOR_ARGS = frozenset(("repetition_penalty", "no_repeat_ngram_size"))
     # the names of _UNSUPPORTED that generate(num_beams > 1) hands to GenerationEngine.generate_beam (csrc/beam.hip); generate() alone passes them
     _BEAM_ARGS = frozenset(("num_beams", "length_penalty", "num_return_sequences"))
+    # the name of _UNSUPPORTED that generate(guidance_scale > 1) hands to GenerationEngine.generate_guided (csrc/cfg.hip); generate() alone passes it
+    _GUIDANCE_ARGS = frozenset(("guidance_scale",))
 
     @classmethod
     def _check_generate_kwargs(cls, kwargs, implemented=frozenset()):

@@ -526,6 +526,25 @@ int crab_beam_merge(crab_ctx* ctx, void* stream, const float* cand_score, const 
                     int32_t* hyp_fin, int32_t* unsat, int64_t* cur_ids, int32_t* beam_idx, int32_t* finished);
 int crab_kv_beam_reorder(crab_ctx* ctx, void* stream, void* k_cache, void* v_cache, int L, int rows, int num_beams, int Hk, int Tmax,
                          int head_dim, int first_slot, const int32_t* pos_dev, const int32_t* beam_idx, const int32_t* finished);
+/* Classifier-free guidance of the step (csrc/cfg.hip): HF's UnbatchedClassifierFreeGuidanceLogitsProcessor without its second model forward
+ * from a host callback.  The conditional and the unconditional prompt of a clip decode as two rows of one ragged batch: pair b < B is row b
+ * (conditional, c) and row B + b (unconditional, u) of the raw fp32 logits [2B, V].
+ * crab_cfg_mix runs BEFORE the select: one block per pair, guided[b, i] = lu + guidance_scale * (lc - lu) with lc = c[i] - logsumexp(c),
+ *     lu = u[i] - logsumexp(u) - HF's scale * (log_softmax(cond) - log_softmax(uncond)) + log_softmax(uncond) - into fp32 guided [B, V]
+ *     (row stride ldg), a buffer of its own: the logits are never written.  The select kernels then run on `guided` with B rows.  Each
+ *     logsumexp is one pass of 16-byte loads (scalar head / tail: any 4-byte aligned base, any ldl >= V), merged in double in a fixed order and
+ *     rounded once to fp32; no float atomics: two runs give the same bits.  An element that is -inf in EITHER row gives -inf (HF gives NaN
+ *     where both are); a NaN logit makes every element of its pair that is not -inf NaN.  A pair with finished[b] != 0 is computed like any
+ *     other: the select kernels scan a finished row too.
+ * crab_cfg_follow runs AFTER the select and before crab_advance: cur_ids[B + b] = cur_ids[b], out_ids[B + b, step] = out_ids[b, step],
+ *     finished[B + b] = finished[b] with step = step_dev[0]; nothing at all when step is outside [0, n_steps).
+ * Neither reads the host; both are capturable.  CRAB_E_INVALID for null operands, B / V < 1, ldl < V, ldg < V, a NaN guidance_scale,
+ * n_steps < 1, ld_out < n_steps.
+ * ADDED under ABI 13 (crab_abi_version() still returns 13: nothing that existed changed); probe for the symbol, not for a version number. */
+int crab_cfg_mix(crab_ctx* ctx, void* stream, const float* logits, int64_t ldl, int B, int V, float guidance_scale, const int32_t* finished,
+                 float* guided, int64_t ldg);
+int crab_cfg_follow(crab_ctx* ctx, void* stream, int64_t* cur_ids, int64_t* out_ids, int64_t ld_out, int n_steps, int32_t* finished,
+                    const int32_t* step_dev, int B);
 
 /* ---------------------------------------------------------------------------------------------
  * Teacher-forced scoring (csrc/xent.hip): the language-model loss of models/modeling_llama.py:1261-1274 as reached from
