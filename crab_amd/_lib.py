@@ -205,6 +205,8 @@ SYMBOLS = {
     "crab_greedy_select": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _i64, _vp, _vp, _i, _i, _i]),
     "crab_advance": (_i, [_vp, _vp, _vp, _vp]),
     "crab_sample_select": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _i64, _vp, _vp, _i, _i, _i, _f, _i, _f, C.c_uint64]),
+    "crab_sample_select_warped": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _i64, _vp, _vp, _i, _i, _i, _f, _i, _f, C.c_uint64, _f, _f, _f, _vp,
+                                       _vp]),
     "crab_constrained_select": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _i, _f, _i, _f,
                                      C.c_uint64]),
     "crab_logprob_norm": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),

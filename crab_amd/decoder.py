@@ -234,6 +234,36 @@ def check_processors(processors, min_new_tokens: int = 0, constrained: bool = Fa
     return proc
 
 
+def normalize_sampling(sampling, constrained: bool = False):
+    """The `sampling` argument of the generate entry points: None (greedy), (temperature, top_k, top_p, seed) or, with HF's further truncation
+    warpers, (temperature, top_k, top_p, seed, min_p, epsilon_cutoff, eta_cutoff) - 0 or None = that stage is off (csrc/sample_warp.hip).
+    A 7-tuple whose three stages are all off comes back as the 4-tuple: that call is the plain sampling call (same state key, same graph,
+    same launches).  Values outside min_p in [0, 1] / the cutoffs in [0, 1), NaN included, raise ValueError by name; a live stage with a
+    token trie (constrained) is refused by name - crab_constrained_select is a kernel of its own.  All before any device work."""
+    if sampling is None or len(sampling) == 4:
+        return sampling
+    if len(sampling) != 7:
+        raise ValueError(f"sampling must be (temperature, top_k, top_p, seed) or those four + (min_p, epsilon_cutoff, eta_cutoff), got {sampling!r}")
+    w = []
+    for name, v, hi_ok in (("min_p", sampling[4], True), ("epsilon_cutoff", sampling[5], False), ("eta_cutoff", sampling[6], False)):
+        v = 0.0 if v is None else float(v)
+        if not (0.0 <= v <= 1.0) or (v == 1.0 and not hi_ok):
+            raise ValueError(f"`{name}` has to be a float in " + ("[0, 1]" if hi_ok else "[0, 1)") + f" (0 = off), but is {v}")
+        w.append(v)
+    if not any(w):
+        return tuple(sampling[:4])
+    if constrained:
+        live = ", ".join(f"{n} = {v}" for n, v in zip(("min_p", "epsilon_cutoff", "eta_cutoff"), w) if v)
+        raise NotImplementedError(f"constraint with {live}: the truncation warpers beyond top_p are not implemented under a token trie "
+                                  "(crab_constrained_select is a kernel of its own; temperature, top_k and top_p are)")
+    return tuple(sampling[:4]) + tuple(w)
+
+
+def reseed_sampling(sampling, offset: int):
+    """The sampling tuple (of either length) of a later wave or group of one call: its seed moved by `offset`, everything else kept."""
+    return None if sampling is None else tuple(sampling[:3]) + (sampling[3] + offset,) + tuple(sampling[4:])
+
+
 def _pack_waves(Bs: List[int], cap: int) -> List[List[int]]:
     """generate_many(coalesce=True): the batches (Bs[g] rows each), in order, as waves of at most `cap` rows and about equal size - 60 batches
     of 8 at cap 448 run as 240 + 240, not 448 + 32.  A batch larger than the cap is a wave of its own.  Returns the batch indices per wave."""
@@ -1081,7 +1111,9 @@ class GenerationEngine:
 
     def _select(self, st: "_DecodeState"):
         """Next token of every row from st.logits: greedy (argmax) or, with st.sampling = (temperature, top_k, top_p, seed), HF's sample
-        mode (temperature -> top-k -> top-p -> draw) - both device-resident, so the step stays capturable.  A state with a token trie (st.trie:
+        mode (temperature -> top-k -> top-p -> draw) - both device-resident, so the step stays capturable.  A sampling tuple that goes on with
+        (min_p, epsilon_cutoff, eta_cutoff), at least one of them live, takes those three stages between top-p and the draw
+        (ops.sample_select_warped); the values are part of the tuple and so of the state key.  A state with a token trie (st.trie:
         closed-set generation) takes both among the out-edges of every row's node instead (ops.constrained_select; st.node follows the edge).
         A state with st.lp (return_logprobs) also records the log-probability of the chosen token: the normalisers of the raw logits are taken
         BEFORE the select (it sets `finished` and moves st.node), the token's logit is gathered AFTER it (ops.logprob_norm / logprob_gather); the
@@ -1128,14 +1160,19 @@ class GenerationEngine:
         state: the select then writes those rows' words."""
         logits = st.logits if logits is None else logits
         if st.trie is not None:
-            t, k, p_, seed = st.sampling if st.sampling is not None else (0.0, 0, 1.0, 0)
+            t, k, p_, seed = st.sampling if st.sampling is not None else (0.0, 0, 1.0, 0)      # never a 7-tuple: normalize_sampling refuses it
             ops.constrained_select(logits, st.trie.edge_off, st.trie.edge_tok, st.trie.edge_dst, st.node, st.cur_ids, st.out_ids, st.step_dev,
                                    st.finished, st.eos, st.pad, st.min_new, t, k, p_, seed + 7919 * st.slot)
         elif st.sampling is None:
             ops.greedy_select(logits, st.cur_ids, st.out_ids, st.step_dev, st.finished, st.eos, st.pad, st.min_new)
-        else:
+        elif len(st.sampling) == 4:
             t, k, p_, seed = st.sampling
             ops.sample_select(logits, st.cur_ids, st.out_ids, st.step_dev, st.finished, st.eos, st.pad, st.min_new, t, k, p_, seed + 7919 * st.slot)
+        else:
+            # a live min_p / epsilon_cutoff / eta_cutoff (normalize_sampling: a 7-tuple holds at least one): csrc/sample_warp.hip
+            t, k, p_, seed, min_p, eps, eta = st.sampling
+            ops.sample_select_warped(logits, st.cur_ids, st.out_ids, st.step_dev, st.finished, st.eos, st.pad, st.min_new, t, k, p_,
+                                     seed + 7919 * st.slot, min_p, eps, eta)
 
     def _state(self, B: int, S: int, max_new_tokens: int, eos_token_id, pad_token_id, min_new_tokens: int, return_hidden: bool, slot: int,
                sampling=None, ragged: bool = False, extra_key=(), constraint=None, logprobs: bool = False, processors=None,
@@ -1386,6 +1423,7 @@ class GenerationEngine:
         constrained call) - HF's compute_transition_scores(normalize_logits=True) of a greedy call.  0.0 where the row emitted no token
         (padding after its EOS; the EOS column itself is a token).  Sample mode: the warpers are a drawing device and enter neither number
         (HF's warped `scores` are not reproduced).  Written inside the decode step (csrc/logprob.hip): no host sync, nothing of size B x V kept."""
+        sampling = normalize_sampling(sampling, constraint is not None)
         proc = check_processors(processors, min_new_tokens, constraint is not None, return_logprobs, eos_token_id)      # refused before any device work
         cons, = self._constraints(constraint, [int(embeds.shape[0])], eos_token_id, min_new_tokens, flat=True)
         return self._call(kv_cache_dtype, weight_dtype, self._generate, embeds, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens,
@@ -1449,7 +1487,9 @@ class GenerationEngine:
         (unified_llama.py:262-267): positions 0..S-1 (left pads attended), returns ONLY new ids.
 
         sampling = (temperature, top_k, top_p, seed): HF sample mode instead of greedy (what the reference actually runs with a Llama-2-chat
-        checkpoint, whose generation_config sets do_sample); None = greedy.
+        checkpoint, whose generation_config sets do_sample); None = greedy.  With three more entries,
+        (..., seed, min_p, epsilon_cutoff, eta_cutoff), HF's further truncation warpers run between top-p and the draw (normalize_sampling;
+        0 / None = off, all three off is the 4-tuple's call; refused by name with a constraint).
 
         return_first_logits: also return the fp32 last-row logits of the prefill ([B, V], one clone per call: what the multi-GPU
         eval gathers next to the ids, crab_amd/parallel.py) without keeping every step's logits.
@@ -1528,6 +1568,7 @@ class GenerationEngine:
         in-flight states and the ragged waves.
         constraint = (TokenTrie, one list of set indices per batch or None): closed-set generation as in generate(); the set indices follow
         their rows into the in-flight states and the ragged waves."""
+        sampling = normalize_sampling(sampling, constraint is not None)
         proc = check_processors(processors, min_new_tokens, constraint is not None, return_logprobs, eos_token_id)
         cons = self._constraints(constraint, [int(e.shape[0]) for e in embeds_list], eos_token_id, min_new_tokens) if constraint is not None else None
         return self._call(kv_cache_dtype, weight_dtype, self._generate_many, embeds_list, max_new_tokens, eos_token_id, pad_token_id,
@@ -1680,8 +1721,8 @@ class GenerationEngine:
         its clip, "visual contrastive decoding"): embeds [B, S, D] are the conditional prompts, negative_embeds [B, Sn, D] the unconditional
         ones, and every token is chosen from
             lu + guidance_scale * (lc - lu),    lc / lu = log_softmax of the conditional / unconditional logits,
-        greedy or, with sampling = (temperature, top_k, top_p, seed), in HF's sample mode (the guided scores go through the warpers, HF's
-        order).  HF runs a second model forward per step from a Python callback; here the two prompts of a clip are two ROWS of one ragged
+        greedy or, with sampling = (temperature, top_k, top_p, seed[, min_p, epsilon_cutoff, eta_cutoff]), in HF's sample mode (the guided
+        scores go through the warpers, HF's order).  HF runs a second model forward per step from a Python callback; here the two prompts of a clip are two ROWS of one ragged
         wave (_start_ragged: conditional rows first, unconditional rows after, each group with its own length, right-aligned in one KV cache),
         so the weights stream once per step for both and the step stays one captured graph: crab_cfg_mix -> the ordinary select on the B
         guided rows -> crab_cfg_follow (csrc/cfg.hip), which hands the unconditional row its pair's token.  An 800-row clip prompt beside a
@@ -1721,6 +1762,7 @@ class GenerationEngine:
         cap = (min(int(max_rows), ops.DECODE_MAX_ROWS) if max_rows else ops.DECODE_MAX_ROWS) // 2
         if cap < 1:
             raise ValueError(f"max_rows = {max_rows}: a pair needs two rows")
+        sampling = normalize_sampling(sampling)
         return self._call(kv_cache_dtype, weight_dtype, self._generate_guided, embeds, negative_embeds, g, int(max_new_tokens), eos_token_id,
                           pad_token_id, int(min_new_tokens), use_graph, sampling, return_step_logits, cap)
 
@@ -1741,7 +1783,7 @@ class GenerationEngine:
         pad = int(pad_token_id) if pad_token_id is not None else (int(eos_token_id) if eos_token_id is not None else 0)
         ids, cond, unc, b0 = [], [], [], 0
         for n in sizes:
-            smp = None if sampling is None else (sampling[0], sampling[1], sampling[2], sampling[3] + 104729 * b0)
+            smp = reseed_sampling(sampling, 104729 * b0)
             out, sl = self._guided_wave(embeds[b0:b0 + n], negative_embeds[b0:b0 + n], scale, max_new_tokens, eos_token_id, pad_token_id,
                                         min_new_tokens, use_graph, smp, return_step_logits)
             ids.append(out)
@@ -1865,6 +1907,7 @@ class GenerationEngine:
         constraint = (TokenTrie, one list per clip with one set index per question, or None): closed-set generation as in generate().
         return_logprobs: every clip's result gains a LAST element, fp32 [G_c, n, 2], as in generate().
         processors = (repetition_penalty, no_repeat_ngram_size, stop_token_ids) or None, as in generate()."""
+        sampling = normalize_sampling(sampling, constraint is not None)
         proc = check_processors(processors, min_new_tokens, constraint is not None, return_logprobs, eos_token_id)
         cons = self._constraints(constraint, [len(qs) for qs in suffix_embeds], eos_token_id, min_new_tokens) if constraint is not None else None
         return self._call(kv_cache_dtype, weight_dtype, self._generate_shared_prefix, prefix_embeds, suffix_embeds, max_new_tokens, eos_token_id,
@@ -2095,7 +2138,7 @@ class GenerationEngine:
                 r = self._generate(embeds[b0:b0 + n], max_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
                                    min_new_tokens=min_new_tokens, prefill_chunk=prefill_chunk, use_graph=use_graph,
                                    return_step_logits=return_step_logits, return_hidden=return_hidden, return_first_logits=return_first_logits,
-                                   sampling=None if sampling is None else (sampling[0], sampling[1], sampling[2], sampling[3] + 104729 * b0),
+                                   sampling=reseed_sampling(sampling, 104729 * b0),
                                    constraint=constraint.rows(b0, b0 + n) if constraint is not None else None, return_logprobs=return_logprobs,
                                    processors=processors)
             finally:

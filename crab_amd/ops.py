@@ -677,6 +677,36 @@ def sample_select(logits, cur_ids, out_ids, step_dev, finished, eos_id: int, pad
                                               int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF), d)
 
 
+def sample_select_warped(logits, cur_ids, out_ids, step_dev, finished, eos_id: int, pad_id: int, min_new_tokens: int, temperature: float, top_k: int,
+                         top_p: float, seed: int, min_p: float = 0.0, epsilon_cutoff: float = 0.0, eta_cutoff: float = 0.0, kept_n=None, kept_min=None):
+    """crab_sample_select_warped (csrc/sample_warp.hip): sample_select with HF's min_p -> epsilon_cutoff -> eta_cutoff stages between top-p and
+    the draw (0 = that stage is off; all three off gives sample_select's ids bit for bit).  logits [B, V] fp32 rows with unit column stride
+    (a row stride of 0 - one row expanded - is fine: the rows are only read); cur_ids int64 [>= B], out_ids int64 [B, n_steps] with unit
+    column stride, step_dev int32 [1], finished int32 [>= B].  kept_n (int32 [>= B]) / kept_min (fp32 [>= B]), each optional: the size of
+    every row's final kept set and the smallest scaled logit in it."""
+    d = _dev(logits)
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1 or logits.stride(0) < 0:
+        raise ValueError(f"logits must be float32 [B, V] rows with unit column stride, got {logits.dtype} {tuple(logits.shape)} strides {logits.stride()}")
+    B, V = logits.shape
+    dev = logits.device
+    if cur_ids.dtype != torch.int64 or cur_ids.dim() != 1 or cur_ids.shape[0] < B or not cur_ids.is_contiguous() or cur_ids.device != dev:
+        raise ValueError(f"cur_ids must be a contiguous int64 [{B}] tensor on {dev}, got {cur_ids.dtype} {tuple(cur_ids.shape)} on {cur_ids.device}")
+    if out_ids.dtype != torch.int64 or out_ids.dim() != 2 or out_ids.shape[0] < B or out_ids.shape[1] < 1 or out_ids.stride(1) != 1 or \
+            out_ids.stride(0) < out_ids.shape[1] or out_ids.device != dev:
+        raise ValueError(f"out_ids must be an int64 [{B}, n_steps] tensor with unit column stride on {dev}, got {out_ids.dtype} "
+                         f"{tuple(out_ids.shape)} strides {out_ids.stride()} on {out_ids.device}")
+    _chk_i32("step_dev", step_dev, 1, dev)
+    _chk_i32("finished", finished, B, dev)
+    _chk_i32("kept_n", kept_n, B, dev)
+    if kept_min is not None and (kept_min.dtype != torch.float32 or kept_min.dim() != 1 or kept_min.shape[0] < B or not kept_min.is_contiguous() or
+                                 kept_min.device != dev):
+        raise ValueError(f"kept_min must be a contiguous float32 [{B}] tensor on {dev}, got {kept_min.dtype} {tuple(kept_min.shape)} on {kept_min.device}")
+    _lib.check(_lib.load().crab_sample_select_warped(_lib.ctx(d), _stream(), _p(logits), logits.stride(0), B, V, _p(cur_ids), _p(out_ids),
+                                                     out_ids.stride(0), _p(step_dev), _p(finished), eos_id, pad_id, min_new_tokens,
+                                                     float(temperature), int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, float(min_p),
+                                                     float(epsilon_cutoff), float(eta_cutoff), _p(kept_n), _p(kept_min)), d)
+
+
 def constrained_select(logits, edge_off, edge_tok, edge_dst, node, cur_ids, out_ids, step_dev, finished, eos_id: int, pad_id: int,
                        min_new_tokens: int, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0):
     """crab_constrained_select: the next token of every row among the out-edges of node[b] in a token trie (CSR int32 arrays, crab_amd/constrain.py),

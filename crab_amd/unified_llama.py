@@ -306,10 +306,20 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
         and do_sample, min_new_tokens, one eos_token_id, both fp8 modes, max_rows.  output_logits + return_dict_in_generate gives the RAW
         logits of the conditional rows.  None and 1 are off.  Refused by name with guidance: num_beams > 1, allowed_sequences,
         output_token_logprobs, output_first_logits, repetition_penalty, no_repeat_ngram_size, several eos ids, decode_streams > 1, a scale
-        below 1.  A token that is -inf in either row scores -inf (HF: NaN where both are)."""
+        below 1.  A token that is -inf in either row scores -inf (HF: NaN where both are).
+        min_p / epsilon_cutoff / eta_cutoff (with do_sample): HF's MinPLogitsWarper, EpsilonLogitsWarper and EtaLogitsWarper, in HF's order
+        after temperature, top_k and top_p - every stage on the distribution renormalised over what the stages before it kept, the largest
+        token and its ties always kept (csrc/sample_warp.hip, inside the decode step).  min_p in (0, 1] removes p_i < min_p * p_max;
+        epsilon_cutoff in (0, 1) removes p_i < eps; eta_cutoff in (0, 1) removes p_i < min(eps, sqrt(eps) * exp(-H)), H the entropy of the
+        current distribution.  None and 0 are off (all three off: the plain sampling call, launch for launch); without do_sample they have
+        no effect, as in HF.  Also in generate_batches / generate_questions / generate_avs*, and with guidance_scale (the guided scores go
+        through them).  A value out of range or NaN raises ValueError by name (HF drops a cutoff outside (0, 1) silently);
+        allowed_sequences with a live one is refused by name; typical_p stays refused."""
         beams =int(kwargs.get("num_beams") or 1)
-        # _GUIDANCE_ARGS is read from the class: generate() alone routes guidance_scale, whatever object stands in for self
-        self._check_generate_kwargs(kwargs, (self._PROCESSOR_ARGS | self._BEAM_ARGS if beams > 1 else self._PROCESSOR_ARGS) | UnifiedForCausalLM._GUIDANCE_ARGS)
+        # _GUIDANCE_ARGS and _WARPER_ARGS are read from the class: generate() alone routes guidance_scale, and _sampling parses the warpers, whatever
+        # object stands in for self
+        self._check_generate_kwargs(kwargs, (self._PROCESSOR_ARGS | self._BEAM_ARGS if beams > 1 else self._PROCESSOR_ARGS) | UnifiedForCausalLM._GUIDANCE_ARGS |
+                                    UnifiedForCausalLM._WARPER_ARGS)
         scale = kwargs.get("guidance_scale")
         if scale is not None and float(scale) != 1.0:          # None and 1 are off (HF adds its processor under the same condition): the plain call below
             return UnifiedForCausalLM._generate_guided(self, batch_input_ids, batch_labels, batch_X_modals, batch_task_names, kwargs)
@@ -466,7 +476,7 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
             if kwargs.get(k) is not None and kwargs.get(k) is not False:
                 raise NotImplementedError(f"generate_batches returns token ids only: {k} is a generate() argument")
         want_first = bool(kwargs.get("output_first_logits"))
-        self._check_generate_kwargs(kwargs, self._PROCESSOR_ARGS)
+        self._check_generate_kwargs(kwargs, self._PROCESSOR_ARGS | UnifiedForCausalLM._WARPER_ARGS)
         sampling = self._sampling(kwargs)
         eos, proc = self._processors(kwargs)
         constraint = self._constraint(kwargs, eos)
@@ -510,7 +520,7 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
                 raise NotImplementedError(f"generate_questions returns token ids only: {k} is a generate() argument")
         want_first = bool(kwargs.get("output_first_logits"))
         want_lp = bool(kwargs.get("output_token_logprobs"))
-        self._check_generate_kwargs(kwargs, self._PROCESSOR_ARGS)
+        self._check_generate_kwargs(kwargs, self._PROCESSOR_ARGS | UnifiedForCausalLM._WARPER_ARGS)
         sampling = self._sampling(kwargs)
         eos, proc = self._processors(kwargs)
         constraint = self._constraint(kwargs, eos)
@@ -559,6 +569,8 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
     _BEAM_ARGS = frozenset(("num_beams", "length_penalty", "num_return_sequences"))
     # the name of _UNSUPPORTED that generate(guidance_scale > 1) hands to GenerationEngine.generate_guided (csrc/cfg.hip); generate() alone passes it
     _GUIDANCE_ARGS = frozenset(("guidance_scale",))
+    # the names of _UNSUPPORTED that _sampling parses (csrc/sample_warp.hip): every entry point that takes do_sample through _sampling passes them
+    _WARPER_ARGS = frozenset(("min_p", "epsilon_cutoff", "eta_cutoff"))
 
     @classmethod
     def _check_generate_kwargs(cls, kwargs, implemented=frozenset()):
@@ -608,12 +620,26 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
     @staticmethod
     def _sampling(kwargs):
         """HF sample-mode arguments -> (temperature, top_k, top_p, seed) or None (greedy).  Defaults = what a Llama-2-chat checkpoint's
-        generation_config + GenerationConfig's own defaults give the reference's generate() call (temperature 0.6, top_p 0.9, top_k 50)."""
+        generation_config + GenerationConfig's own defaults give the reference's generate() call (temperature 0.6, top_p 0.9, top_k 50).
+        min_p / epsilon_cutoff / eta_cutoff (_WARPER_ARGS; HF's MinP-, Epsilon- and EtaLogitsWarper, csrc/sample_warp.hip) are parsed and
+        validated here - this is the one function every entry point that samples goes through: a live one makes the result the 7-tuple
+        (temperature, top_k, top_p, seed, min_p, epsilon_cutoff, eta_cutoff)."""
+        warp = []
+        for name, closed in (("min_p", True), ("epsilon_cutoff", False), ("eta_cutoff", False)):
+            v = kwargs.get(name)
+            v = 0.0 if v is None else float(v)
+            if not (0.0 <= v <= 1.0) or (v == 1.0 and not closed):      # NaN fails the first test; HF drops a cutoff outside (0, 1) silently
+                raise ValueError(f"`{name}` has to be a float in " + ("[0, 1]" if closed else "[0, 1)") + f" (None and 0 are off), but is {v}")
+            warp.append(v)
         if not kwargs.get("do_sample"):
-            return None
+            return None                                        # HF builds warpers in sample mode only: the three have no effect on a greedy call
         t, k, p_ = float(kwargs.get("temperature", 0.6)), int(kwargs.get("top_k", 50) or 0), float(kwargs.get("top_p", 0.9))
         if t <= 0 or not (0 < p_ <= 1) or k < 0:
             raise ValueError("do_sample: temperature > 0, 0 < top_p <= 1, top_k >= 0")
+        if any(warp) and kwargs.get("allowed_sequences") is not None:
+            live = ", ".join(f"{n}={v}" for n, v in zip(("min_p", "epsilon_cutoff", "eta_cutoff"), warp) if v)
+            raise NotImplementedError(f"generate(allowed_sequences=..., {live}): the truncation warpers beyond top_p are not implemented in a closed-set "
+                                      "call (crab_constrained_select is a kernel of its own; temperature, top_k and top_p are)")
         seed = kwargs.get("seed")
         if seed is None:
             # no explicit seed: like HF (whose torch.multinomial advances the global generator) every call draws a fresh stream - the seed is
@@ -621,7 +647,8 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
             # no longer return the same sample.  seed=<int> stays fully deterministic per call.  (The seed is baked into the captured decode
             # graph: an unseeded sampling call re-captures it.)
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        return (t, k, p_, int(seed) & 0x7FFFFFFFFFFFFFFF)
+        base = (t, k, p_, int(seed) & 0x7FFFFFFFFFFFFFFF)
+        return base + tuple(warp) if any(warp) else base       # all three off: the 4-tuple, i.e. the plain sampling call, key and launches
 
     @torch.no_grad()
     def generate_avs(self, batch_input_ids, batch_labels, batch_X_modals, batch_task_names, **kwargs):
@@ -681,7 +708,7 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
 
     def _avs_generate(self, samples, max_rows, kwargs):
         """First half of generate_avs_many: inputs of every call (multi-scale CLIP features kept) and the ragged decode with per-step hidden states."""
-        self._check_generate_kwargs(kwargs, self._PROCESSOR_ARGS)
+        self._check_generate_kwargs(kwargs, self._PROCESSOR_ARGS | UnifiedForCausalLM._WARPER_ARGS)
         sampling = self._sampling(kwargs)
         eos, proc = self._processors(kwargs)
         if ops.PROFILER is not None:

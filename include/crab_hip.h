@@ -416,6 +416,24 @@ int crab_advance(crab_ctx* ctx, void* stream, int32_t* pos_dev, int32_t* step_de
 int crab_sample_select(crab_ctx* ctx, void* stream, const float* logits, int64_t ldl, int B, int V, int64_t* cur_ids,
                        int64_t* out_ids, int64_t ld_out, const int32_t* step_dev, int32_t* finished, int eos_id, int pad_id,
                        int min_new_tokens, float temperature, int top_k, float top_p, uint64_t seed);
+/* crab_sample_select with HF's three further truncation warpers between top-p and the draw (csrc/sample_warp.hip), in HF's order:
+ * temperature -> top_k -> top_p -> min_p -> epsilon_cutoff -> eta_cutoff -> draw.  Every stage sees the distribution renormalised over what
+ * the stages before it kept, and the largest token with its exact ties always stays (min_tokens_to_keep = 1):
+ *   min_p          in [0, 1], 0 = off: removes token i when p_i < min_p * p_max               (MinPLogitsWarper)
+ *   epsilon_cutoff in [0, 1), 0 = off: removes p_i < epsilon_cutoff                           (EpsilonLogitsWarper)
+ *   eta_cutoff     in [0, 1), 0 = off: removes p_i < min(eta_cutoff, sqrt(eta_cutoff) * exp(-H)), H the natural-log entropy of the current
+ *                  distribution, removed tokens contributing 0                                (EtaLogitsWarper)
+ * A token at -inf has no mass and passes no live stage; a row without a finite token emits token 0 as crab_sample_select does.  The
+ * generator, its keying by (seed, step_dev[0], row), the summation tree, EOS / min_new_tokens / finished / pad are crab_sample_select's:
+ * with all three stages off the ids are equal to its ids bit for bit.  kept_n (int32 [B]) and kept_min (fp32 [B]), each null when not
+ * wanted: the number of tokens in the final kept set - exactly the tokens the draw walks - and the smallest scaled logit
+ * (logit * (1 / temperature), -inf for EOS under min_new_tokens) among them; both are written for finished rows too.
+ * CRAB_E_INVALID, with the argument's name in the message, for null operands, B / V < 1, crab_sample_select's ranges, min_p outside [0, 1],
+ * a cutoff outside [0, 1) and NaN.  ADDED under ABI 13 (crab_abi_version() still returns 13); probe for the symbol. */
+int crab_sample_select_warped(crab_ctx* ctx, void* stream, const float* logits, int64_t ldl, int B, int V, int64_t* cur_ids,
+                              int64_t* out_ids, int64_t ld_out, const int32_t* step_dev, int32_t* finished, int eos_id, int pad_id,
+                              int min_new_tokens, float temperature, int top_k, float top_p, uint64_t seed, float min_p,
+                              float epsilon_cutoff, float eta_cutoff, int32_t* kept_n, float* kept_min);
 /* The same step CONSTRAINED to a closed set of answers (csrc/constrain.hip): what HF does with PrefixConstrainedLogitsProcessor
  * (generation/logits_process.py: every token prefix_allowed_tokens_fn does not return is set to -inf) - without the host callback, which cannot run
  * between two replays of a captured step.  The answers are a token trie in CSR form (crab_amd/constrain.py): node n has the out-edges
