@@ -221,6 +221,9 @@ SYMBOLS = {
     "crab_kv_beam_reorder": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "crab_cfg_mix": (_i, [_vp, _vp, _vp, _i64, _i, _i, _f, _vp, _vp, _i64]),
     "crab_cfg_follow": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _vp, _i]),
+    "crab_attn_verify": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _vp, _f, _vp]),
+    "crab_lookup_draft": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "crab_lookup_accept": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "crab_lm_head_xent_workspace": (_i64, [_i, _i]),
     "crab_lm_head_xent": (_i, [_vp, _vp, _vp, _i64, _vp, _i, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _i64]),
     "crab_xent_reduce": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),

@@ -14,8 +14,8 @@ for f in *.hip; do
     extra=""
     # attn.hip: keep the MFMA accumulators in VGPRs.  The flash kernels rescale O every K/V tile; with AGPR accumulators that is
     # 32 v_accvgpr_read + 32 v_mov around 32 multiplies per tile (CLIP shape 150 -> 126 us, decoder shape 217 -> 213 us)
-    # (attn_prefix.hip: its score MFMAs hand their result straight to a vector store, same form)
-    if [ "$f" = "attn.hip" ] || [ "$f" = "attn_prefix.hip" ]; then extra="-mllvm -amdgpu-mfma-vgpr-form"; fi
+    # (attn_prefix.hip and attn_verify.hip: their score MFMAs hand their result straight to a vector store, same form)
+    if [ "$f" = "attn.hip" ] || [ "$f" = "attn_prefix.hip" ] || [ "$f" = "attn_verify.hip" ]; then extra="-mllvm -amdgpu-mfma-vgpr-form"; fi
     /opt/rocm/bin/hipcc $FLAGS $extra -c "$f" -o "$o" &
     pids+=($!)
   fi

@@ -720,7 +720,8 @@ class GenerationEngine:
     def _layers(self, ws: _Workspace, B: int, S: int, kc: torch.Tensor, vc: torch.Tensor, b0: int, Tmax: int, pos0: int,
                 pos_dev: Optional[torch.Tensor], vt: Optional[torch.Tensor], pos_ids: Optional[torch.Tensor] = None,
                 kv_start: Optional[torch.Tensor] = None, key_mask: Optional[torch.Tensor] = None, t0: int = 0,
-                row_off: Optional[torch.Tensor] = None, last_rows: bool = False, kv_scales=None, w8: bool = False, prefix=None):
+                row_off: Optional[torch.Tensor] = None, last_rows: bool = False, kv_scales=None, w8: bool = False, prefix=None,
+                verify: bool = False):
         """x (ws.x[:B*S]) -> x after all layers.  w8 (decode steps of generate() only, <= 16 rows): the projections stream the FP8 weights.  Prefill when vt is given (S rows per sequence, positions pos0..),
         decode otherwise (S == 1, position read from pos_dev).  kc/vc: [L, Btot, Hk, Tmax, d]; rows b0..b0+B.
         The RAGGED decode batch (generate_many(coalesce=True)): sequences of different prompt lengths are right-aligned in one cache - a
@@ -740,7 +741,10 @@ class GenerationEngine:
         crab_attn_prefix_partial + crab_attn_own_merge.  Decode step (vt None, S == 1): row_off = first own slot of every row (the first visible
         key), prefix.rope_off = that minus P (the rotary offset: slot - rope_off = position, a NEGATIVE word - crab_qkv_rope_split_ragged only
         subtracts it).  Suffix prefill (vt None, S > 1): pos_ids = the rotary positions, kv_start = the first own slot; query s sees the own
-        slots kv_start[b] .. pos0 + s."""
+        slots kv_start[b] .. pos0 + s.
+        verify (generate_lookup): the verify step of prompt-lookup decoding - vt None, S = k + 1 <= 16 rows of ONE sequence at the slots
+        pos_dev + pos0 + s: the M <= 16 projection kernels, crab_qkv_rope_split with S rows and the device position word, then
+        crab_attn_verify (row s sees the slots 0 .. pos_dev + pos0 + s).  Per-launch sequence, bf16 cache and weights."""
         c = self.cfg
         H, Hk, d = c.num_attention_heads, c.num_key_value_heads, c.head_dim
         M = B * S
@@ -760,6 +764,9 @@ class GenerationEngine:
                 raise NotImplementedError('weight_dtype="fp8_e4m3" with a shared prefix (generate_shared_prefix) is not implemented')
             if vt is not None or key_mask is not None or t0 or b0 or last_rows or (S == 1) != (row_off is not None) or (S > 1) != (pos_ids is not None and kv_start is not None):
                 raise ValueError("prefix=: a decode step takes row_off, the suffix prefill pos_ids and kv_start; rows 0 .. B - 1, no V^T, no key mask")
+        if verify and (vt is not None or pos_dev is None or not 1 <= S <= 16 or prefix is not None or kv_scales is not None or w8 or row_off is not None
+                       or pos_ids is not None or kv_start is not None or key_mask is not None or last_rows or t0):
+            raise ValueError("verify=: S <= 16 rows per sequence at pos_dev + pos0 + s, bf16 cache and weights, no masks, no prefix")
         x, h, qkv, att, act = ws.x[:M], ws.h[:M], ws.qkv[:M], ws.att[:M], ws.act[:M]
         tab = self._rope_tab(Tmax if prefix is None else prefix.P + Tmax)
         scale = 1.0 / math.sqrt(d)
@@ -780,12 +787,13 @@ class GenerationEngine:
         native_ok = key_mask is None and (not masked or (vt is not None and pos_dev is None and
                                                          (pos_ids is None or (pos_ids.dtype == torch.int32 and pos_ids.stride(1) == 1))))
         last_rows = bool(last_rows) and vt is not None and S > 1 and key_mask is None and pos_dev is None
-        if prefix is None and NATIVE_LAYERS and not timed and native_ok and contig and (vt is not None or S == 1):
+        if prefix is None and not verify and NATIVE_LAYERS and not timed and native_ok and contig and (vt is not None or S == 1):
             self._layers_native(ws, B, S, kc, vc, b0, Tmax, pos0, pos_dev, vt, t0, row_off, pos_ids, kv_start, last_rows, kv_scales, w8)
             return x, h
         u_qkv = None                                   # router output for the q|k|v group when a producer epilogue made it
         # small batch: the projection leaves its raw row, ONE launch does RoPE + KV append + split-context attention (as csrc/llama_layer.hip)
-        aw = self._attn_scratch(ws, B) if (vt is None and S == 1 and not masked and row_off is None and contig and kv_scales is None and prefix is None) else None
+        aw = self._attn_scratch(ws, B) if (vt is None and S == 1 and not masked and row_off is None and contig and kv_scales is None and prefix is None
+                                           and not verify) else None
         fuse_attn = aw is not None and aw.numel() >= ops.attn_decode_rope_bytes(B, H, d)
         for li, layer in enumerate(layers):
             a, m = layer.self_attn, layer.mlp
@@ -803,6 +811,10 @@ class GenerationEngine:
                                    row_off=prefix.rope_off if S == 1 else None)
             elif fuse_attn or kv_scales is not None:
                 a._qkv(h, out=qkv, t_buf=ws.t, u_buf=ws.u, u_ready=u_qkv, fp8=w8)
+            elif verify:
+                # the k + 1 rows of a verify step: RoPE + KV append as their own pass (slot = pos_dev + pos0 + s)
+                a._qkv(h, out=qkv, t_buf=ws.t, u_buf=ws.u, u_ready=u_qkv)
+                ops.qkv_rope_split(qkv, tab, kcl, vcl, None, B, S, H, Hk, d, Tmax, pos0=pos0, pos_dev=pos_dev)
             elif vt is None and S == 1 and lcontig and not masked:
                 # decode: RoPE + KV append ride on the q|k|v projection (fused into its split-K reduction when it has one)
                 a._qkv(h, out=qkv, t_buf=ws.t, u_buf=ws.u, u_ready=u_qkv, rope=(tab, kcl, vcl, H, Hk, d, Tmax, pos0, pos_dev), rope_row_off=row_off, fp8=w8)
@@ -824,6 +836,8 @@ class GenerationEngine:
                 ops.attn_prefix_partial(qkv, prefix.pk[li], prefix.pv[li], prefix.ws, prefix.tile_rows, prefix.row_clip, M, H, Hk, d, prefix.P, scale)
                 ops.attn_own_merge(qkv, prefix.ws, kcl, vcl, att, B, S, H, Hk, d, Tmax, pos0 + 1, scale, ctx_dev=pos_dev,
                                    kv_start=row_off if S == 1 else kv_start)
+            elif verify:
+                ops.attn_verify(qkv, kcl, vcl, att, B, S, H, Hk, d, Tmax, pos0 + 1, scale, ctx_dev=pos_dev)
             elif vt is not None:
                 Sp = vt.shape[-1]
                 ops.attn_fwd(qkv, kcl, vt, att, q_strides=(S * ldq, d, ldq), k_strides=(Hk * Tmax * d, Tmax * d, d),
@@ -1097,6 +1111,8 @@ class GenerationEngine:
 
     def _decode_step(self, st: "_DecodeState"):
         """One greedy step entirely on device: embed(cur_ids) -> layers -> norm -> lm_head -> greedy select -> advance."""
+        if st.lookup is not None:
+            return self._lookup_step(st)
         c = self.cfg
         B = st.B
         ws = st.ws
@@ -1108,6 +1124,20 @@ class GenerationEngine:
             ops.copy_rows(hfin, st.hn, B, hfin.shape[1])
         self._select(st)
         ops.advance(st.pos_dev, st.step_dev)
+
+    def _lookup_step(self, st: "_DecodeState"):
+        """One verify step of prompt-lookup decoding (generate_lookup), entirely on device: draft k tokens from the history -> embed
+        [current ; drafts] -> layers over the k + 1 rows -> lm_head -> accept (1 .. k + 1 tokens emitted; pos / step advance by that many).
+        A finished state runs the same launches and changes nothing, so the step loop and its EOS check are _run_steps' own."""
+        lk = st.lookup
+        M = lk.k + 1
+        V = lk.logits.shape[1]
+        ops.lookup_draft(lk.hist, st.S, st.step_dev, st.cur_ids, lk.k, lk.max_ngram, st.eos, st.pad, lk.max_new, V, lk.ids, lk.n_draft, st.finished)
+        ops.embedding(lk.ids, self.model.embed_tokens.weight, out=st.ws.x[:M])
+        x, hfin = self._layers(st.ws, 1, M, st.kc, st.vc, 0, st.Tmax, 0, st.pos_dev, None, verify=True)
+        ops.gemm(hfin, self.lm_head.weight, out=lk.logits)
+        ops.lookup_accept(lk.logits, lk.ids, lk.n_draft, st.cur_ids, st.out_ids, lk.hist, st.S, st.pos_dev, st.step_dev, st.finished, st.eos, st.pad,
+                          st.min_new, lk.max_new, lk.stats, lk.step_logits)
 
     def _select(self, st: "_DecodeState"):
         """Next token of every row from st.logits: greedy (argmax) or, with st.sampling = (temperature, top_k, top_p, seed), HF's sample
@@ -1176,7 +1206,7 @@ class GenerationEngine:
 
     def _state(self, B: int, S: int, max_new_tokens: int, eos_token_id, pad_token_id, min_new_tokens: int, return_hidden: bool, slot: int,
                sampling=None, ragged: bool = False, extra_key=(), constraint=None, logprobs: bool = False, processors=None,
-               cfg=None) -> "_DecodeState":
+               cfg=None, lookup=None) -> "_DecodeState":
         """The persistent decode state of `slot` for B sequences whose (longest) prompt has S rows: KV cache, per-row words, logits and the HIP
         graph captured over them.  Kept per slot and reused by every call whose shapes, flags and buffers are the same: the key holds
         everything the captured launches bake in (pointers included).  ragged: the state of a coalesced batch (generate_many(coalesce=True)) -
@@ -1191,12 +1221,19 @@ class GenerationEngine:
         cfg: (guidance_scale, pairs) or None - classifier-free guidance (generate_guided): the B = 2 * pairs rows are the conditional rows and
         then their unconditional ones, the state owns st.guided [pairs, V] fp32 (the scores the select reads, crab_cfg_mix) and _select
         takes the guided route.  The scale is baked into the captured launch, so both values enter the key; st.guided is born with the
-        state and dies with it."""
+        state and dies with it.
+        lookup: (k, max_ngram, keep step logits) or None - prompt-lookup decoding (generate_lookup, B == 1): a verify step appends k + 1 cache rows
+        and runs k + 1 rows through the layers, so Tmax = round_up(S + max_new_tokens + k, 64), the decode workspace is made for k + 1 rows and
+        the logits buffer holds k + 1 rows (st.logits, what the prefill and the first select use, is its first row).  The state owns st.lookup
+        (_Lookup: history, draft ids, counters).  All three values enter the key, and so does S: the history is sized S + max_new_tokens and the
+        captured draft / accept launches bake S in as a host integer (a plain state meets S only through pos_dev; Tmax alone would let two
+        prompt lengths of one 64-row bucket share a state)."""
         if int(max_new_tokens) < 1:                             # HF: GenerationConfig.validate() - "`max_new_tokens` must be greater than 0"; here the first token's slot would not exist
             raise ValueError(f"`max_new_tokens` must be greater than 0, but is {max_new_tokens}.")
         dev = self.device
         D = self.cfg.hidden_size
-        Tmax = _round_up(S + max_new_tokens, 64)
+        lk_rows = (int(lookup[0]) + 1) if lookup is not None else 1
+        Tmax = _round_up(S + max_new_tokens + lk_rows - 1, 64)
         kv = self.alloc_cache(B, Tmax, slot=slot)
         kc, vc = kv[0], kv[1]
         ks, vs = (kv[2], kv[3]) if len(kv) == 4 else (None, None)          # fp8 mode: the row scales beside the codes
@@ -1217,7 +1254,7 @@ class GenerationEngine:
         if proc is not None and int(max_new_tokens) > ops.LOGITS_PROC_MAX_STEPS:
             raise NotImplementedError(f"processors with max_new_tokens = {max_new_tokens}: crab_logits_edit holds at most {ops.LOGITS_PROC_MAX_STEPS} generated tokens")
         pad = int(pad_token_id) if pad_token_id is not None else (eos if eos >= 0 else (stops[0] if stops else 0))
-        ws = self._workspace(B, slot, decode=True)
+        ws = self._workspace(B * lk_rows, slot, decode=True)
         tab = self._rope_tab(Tmax)
         # the weight mode of this state's decode steps; the FP8 forms are (re)built here, before any capture, and their pointers enter the key
         w8 = self._w8_rows(B)
@@ -1229,7 +1266,8 @@ class GenerationEngine:
                self.model.layers[0].self_attn._qkv.RA is not None, sampling, bool(ragged),
                self._kv_mode, ks.data_ptr() if ks is not None else 0, vs.data_ptr() if vs is not None else 0, w8_key, bool(logprobs)) + tuple(extra_key) + \
             (constraint.dev.key if constraint is not None else ()) + (("proc",) + proc if proc is not None else ()) + \
-            (("cfg", float(cfg[0]), int(cfg[1])) if cfg is not None else ())
+            (("cfg", float(cfg[0]), int(cfg[1])) if cfg is not None else ()) + \
+            (("lookup", int(lookup[0]), int(lookup[1]), bool(lookup[2]), int(S)) if lookup is not None else ())
         st = self._dec.get(slot)
         if st is None or st.key != key:
             st = _DecodeState()
@@ -1237,7 +1275,8 @@ class GenerationEngine:
             st.B, st.Tmax, st.kc, st.vc, st.slot, st.ws = B, Tmax, kc, vc, slot, ws
             st.ks, st.vs = ks, vs
             st.w8 = w8
-            st.logits = torch.empty((B, V), device=dev, dtype=torch.float32)
+            st.lookup = _Lookup(dev, S, int(max_new_tokens), int(lookup[0]), int(lookup[1]), V, bool(lookup[2])) if lookup is not None else None
+            st.logits = torch.empty((B, V), device=dev, dtype=torch.float32) if lookup is None else st.lookup.logits[:B]
             st.hn = torch.empty((B, D), device=dev, dtype=BF16)
             st.cur_ids = torch.empty((B,), device=dev, dtype=torch.int64)
             st.out_ids = torch.empty((B, max_new_tokens), device=dev, dtype=torch.int64)
@@ -1268,6 +1307,8 @@ class GenerationEngine:
         st.pos_dev.fill_(S - 1); st.step_dev.zero_()
         if st.lp is not None:
             st.lp.zero_()
+        if st.lookup is not None:
+            st.lookup.reset(pad)
         if constraint is not None:
             assert len(constraint.roots) == B, "one trie root per row"
             st.node.copy_(torch.tensor(constraint.roots, dtype=torch.int32))
@@ -1288,11 +1329,12 @@ class GenerationEngine:
         ops.kv_quant_fp8(sk, sv, st.kc, st.vc, st.ks, st.vs, b0=b0, t0=0, t_dst=t0, S=S, row_off=kv_start)
 
     def _start(self, embeds: torch.Tensor, max_new_tokens: int, eos_token_id, pad_token_id, min_new_tokens: int, prefill_chunk: int,
-               return_hidden: bool, slot: int, sink=None, sampling=None, constraint=None, logprobs: bool = False, processors=None) -> "_DecodeState":
+               return_hidden: bool, slot: int, sink=None, sampling=None, constraint=None, logprobs: bool = False, processors=None,
+               lookup=None) -> "_DecodeState":
         """Allocate the decode state of one group of sequences, prefill it and select its first token."""
         B, S, D = embeds.shape
         st = self._state(B, S, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, return_hidden, slot, sampling, constraint=constraint,
-                         logprobs=logprobs, processors=processors)
+                         logprobs=logprobs, processors=processors, lookup=lookup)
         # ---- prefill in chunks of sequences (bounds activation memory, keeps GEMM M in the MFMA-efficient range)
         chunks = self.plan_prefill_chunks(B, S) if not prefill_chunk else [prefill_chunk] * (B // prefill_chunk) + \
             ([B % prefill_chunk] if B % prefill_chunk else [])
@@ -1436,7 +1478,7 @@ class GenerationEngine:
         graphed: every state's step is captured under its own scratch slot (or its graph reused, _capture) and replayed; else the step runs
         eagerly.  side_streams: every state steps on a HIP stream of its own, forked from the current stream before the first step and joined
         to it after the last; else all steps go to the current stream.  The loop holds no host synchronisation but the EOS check: every
-        EOS_CHECK_EVERY steps the `finished` flags are read, and
+        EOS_CHECK_EVERY steps (a lookup state: every step) the `finished` flags are read, and
           retire = True:  a state whose rows have all finished stops stepping (generate_many: HF stops that call);
           retire = False: every state keeps stepping until ALL of them have finished (generate(decode_streams > 1): the groups are one call,
                           their buffers are joined column by column).
@@ -1451,7 +1493,10 @@ class GenerationEngine:
         if side_streams:
             for sg in streams:
                 sg.wait_stream(main)
-        eos_on = any(e >= 0 for e in sts[0].eos_all)
+        eos_on = any(e >= 0 for e in sts[0].eos_all) or sts[0].lookup is not None      # a lookup state finishes early by max_new_tokens as well
+        # a verify step of a lookup state emits up to k + 1 tokens, so the call can end at ANY step, and every step past its end is a whole
+        # (k + 1)-row pass over the weights that changes nothing: such a state is read after every step (one 4-byte read against a >= 4 ms step)
+        check_every = 1 if sts[0].lookup is not None else EOS_CHECK_EVERY
         live = list(range(len(sts)))
         for step in range(1, max_new_tokens):
             for g in live:
@@ -1463,7 +1508,7 @@ class GenerationEngine:
                         graphs[g].replay()
             if on_step is not None:
                 on_step(sts[0])
-            if eos_on and step % EOS_CHECK_EVERY == 0:
+            if eos_on and step % check_every == 0:
                 still = []
                 for g in live:
                     if still and not retire:
@@ -2000,6 +2045,77 @@ class GenerationEngine:
             r0 = r1
         return outs
 
+    # ------------------------------------------------------------------ prompt-lookup speculative decoding: k draft tokens verified per step
+    @torch.no_grad()
+    def generate_lookup(self, embeds: torch.Tensor, max_new_tokens: int, num_draft_tokens: int, max_ngram: int = 2, prompt_ids=None,
+                        eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, min_new_tokens: int = 0, use_graph: bool = True,
+                        return_first_logits: bool = False, return_step_logits: bool = False, return_stats: bool = False, sampling=None,
+                        processors=None, constraint=None, return_logprobs: bool = False, return_hidden: bool = False,
+                        kv_cache_dtype: Optional[str] = None, weight_dtype: Optional[str] = None):
+        """Greedy generation of ONE sequence (embeds [1, S, D]) with prompt-lookup speculative decoding - HF generate(prompt_lookup_num_tokens =
+        num_draft_tokens, max_matching_ngram_size = max_ngram): every step drafts up to k tokens (the continuation of the earliest earlier
+        occurrence of the history's last n-gram), runs [current token ; drafts] through the decoder as k + 1 rows - ONE read of the weights -
+        and keeps the leading drafts the model agrees with plus its own next token.  The ids are those of generate() under the rule this
+        engine uses wherever another row count selects other kernels (the logits differ within the decoder's bf16 bound).
+        prompt_ids: int [S], the token id of every prompt row, -1 for a row that is no text token (a modality embedding); None: the history
+        starts empty (HF's generate(inputs_embeds=...) starts from an empty input_ids too) and only the generated tokens are matched.  It is
+        metadata of the drafts alone: it changes how many are accepted, never what is emitted.
+        Prefill and the first token are generate()'s (_start); the step (_lookup_step) is captured as one HIP graph and driven by _run_steps.
+        Returns ids [1, n] (trimmed by _trim_at_eos); then, in this order, the emitted tokens' logits fp32 [1, n, V] (return_step_logits), the
+        prefill's last-row logits fp32 [1, V] (return_first_logits), and the counters (return_stats): a dict with verify_steps,
+        drafts_proposed, drafts_accepted, tokens_emitted (the first token, which the prefill emits, is not counted).
+        Refused by name before any device work (check_lookup): more than one row, sampling, processors, constraint, return_logprobs,
+        return_hidden, kv_cache_dtype = "fp8_e4m3", weight_dtype = "fp8_e4m3"; num_draft_tokens outside 1 .. 15 and max_ngram < 1 raise
+        ValueError."""
+        if embeds.dim() != 3:
+            raise ValueError("embeds must be a [1, S, D] tensor")
+        kv = self.check_kv_cache_dtype(kv_cache_dtype) if kv_cache_dtype is not None else self._kv_mode
+        wd = self.check_weight_dtype(weight_dtype) if weight_dtype is not None else getattr(self, "_w_mode", "bf16")
+        k, n = check_lookup(num_draft_tokens, max_ngram, int(embeds.shape[0]), normalize_sampling(sampling), processors, constraint, return_logprobs,
+                            return_hidden, kv, wd)
+        S = int(embeds.shape[1])
+        if prompt_ids is not None:
+            prompt_ids = torch.as_tensor(prompt_ids).reshape(-1)
+            if prompt_ids.numel() != S or prompt_ids.dtype.is_floating_point or prompt_ids.dtype == torch.bool:
+                raise ValueError(f"prompt_ids must hold one integer id per prompt row ({S}; -1 = no text token), got {tuple(prompt_ids.shape)} {prompt_ids.dtype}")
+        return self._call(kv_cache_dtype, weight_dtype, self._generate_lookup, embeds, max_new_tokens, k, n, prompt_ids, eos_token_id, pad_token_id,
+                          min_new_tokens, use_graph, return_first_logits, return_step_logits, return_stats)
+
+    def _generate_lookup(self, embeds, max_new_tokens, k, max_ngram, prompt_ids, eos_token_id, pad_token_id, min_new_tokens, use_graph,
+                         return_first_logits, return_step_logits, return_stats):
+        S = int(embeds.shape[1])
+        firsts = []
+
+        def sink(st):                                          # the first token's logits: row 0 of the kept rows, and the caller's copy
+            if return_first_logits:
+                firsts.append(st.logits.clone())
+            if st.lookup.step_logits is not None:
+                st.lookup.step_logits[:1].copy_(st.logits)
+
+        with _ws_slot(0):
+            st = self._start(embeds, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, 0, False, 0, sink,
+                             lookup=(k, max_ngram, bool(return_step_logits)))
+            lk = st.lookup
+            if prompt_ids is not None:
+                lk.hist[:S].copy_(prompt_ids.to(torch.int32))
+            lk.hist[S:S + 1].copy_(st.out_ids[0, :1])           # the first token (the prefill's): the history's last entry, the current token
+            if int(max_new_tokens) == 1:
+                st.finished.fill_(1)
+        self.last_plan = {"B": 1, "groups": [1], "mode": "lookup", "num_draft_tokens": k, "max_ngram": max_ngram, "Tmax": st.Tmax}
+        # every verify step emits at least one token: max_new_tokens - 1 steps always suffice; _run_steps reads `finished` after every step of a lookup state
+        self._run_steps([st], max_new_tokens, use_graph and max_new_tokens > 2, False, True)
+        n_done = int(st.step_dev.item())
+        out = _trim_at_eos(st.out_ids, n_done, st.eos_all).clone()
+        res = [out]
+        if return_step_logits:
+            res.append(lk.step_logits[None, : out.shape[1]].clone())
+        if return_first_logits:
+            res.append(firsts[0])
+        if return_stats:
+            s = lk.stats.tolist()
+            res.append({"verify_steps": s[0], "drafts_proposed": s[1], "drafts_accepted": s[2], "tokens_emitted": s[3]})
+        return res[0] if len(res) == 1 else tuple(res)
+
     # ------------------------------------------------------------------ beam search: the beams of a clip on one prefix KV
     @torch.no_grad()
     def generate_beam(self, embeds: torch.Tensor, num_beams: int, max_new_tokens: int, eos_token_id: Optional[int] = None,
@@ -2167,7 +2283,8 @@ class GenerationEngine:
             return st.graph
         # warm-up run outside capture is not possible without mutating state; instead snapshot and restore
         snap = (st.cur_ids.clone(), st.out_ids.clone(), st.finished.clone(), st.pos_dev.clone(), st.step_dev.clone(),
-                st.node.clone() if st.node is not None else None)
+                st.node.clone() if st.node is not None else None,
+                (st.lookup.hist.clone(), st.lookup.stats.clone()) if st.lookup is not None else None)
         if st.beam is not None:
             st.finished.fill_(1)                       # a beam step permutes its state and the cache in place: the warm-up runs with every clip done (frozen)
         s = torch.cuda.Stream()
@@ -2182,6 +2299,8 @@ class GenerationEngine:
         st.pos_dev.copy_(snap[3]); st.step_dev.copy_(snap[4])
         if st.node is not None:
             st.node.copy_(snap[5])                     # the warm-up walked the trie one edge ahead of the ids
+        if st.lookup is not None:
+            st.lookup.hist.copy_(snap[6][0]); st.lookup.stats.copy_(snap[6][1])      # the warm-up verify step emitted tokens and counted them
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             self._decode_step(st)
@@ -2197,6 +2316,61 @@ def _lp_rows(st: "_DecodeState", r0: int, r1: int, n: int) -> torch.Tensor:
     """The scores of rows r0 .. r1 of a state for the n columns its ids were trimmed to, as a fresh [r1 - r0, n, 2] tensor (st.lp is the
     persistent, graph-baked buffer the next call refills)."""
     return st.lp[:, r0:r1, :n].permute(1, 2, 0).contiguous()
+
+
+class _Lookup:
+    """The device words of a prompt-lookup state (generate_lookup; csrc/lookup.hip): hist int32 [S + max_new] - the prompt's ids (-1: no text
+    token) and then the emitted tokens; ids int64 [k + 1] - current token, drafts, pad; n_draft; stats int32 [4] - verify steps, drafts
+    proposed, drafts accepted, tokens emitted; logits fp32 [k + 1, V]; step_logits fp32 [max_new, V] when the call keeps the emitted tokens'
+    logits.  Born with the decode state and baked into its captured step."""
+
+    def __init__(self, dev, S: int, max_new: int, k: int, max_ngram: int, V: int, keep_logits: bool):
+        self.k, self.max_ngram, self.max_new = k, max_ngram, max_new
+        self.hist = torch.empty((S + max_new,), device=dev, dtype=torch.int32)
+        self.ids = torch.zeros((k + 1,), device=dev, dtype=torch.int64)
+        self.n_draft = torch.zeros((1,), device=dev, dtype=torch.int32)
+        self.stats = torch.zeros((4,), device=dev, dtype=torch.int32)
+        self.logits = torch.empty((k + 1, V), device=dev, dtype=torch.float32)
+        self.step_logits = torch.zeros((max_new, V), device=dev, dtype=torch.float32) if keep_logits else None
+
+    def reset(self, pad: int):
+        self.hist.fill_(-1); self.ids.fill_(pad); self.n_draft.zero_(); self.stats.zero_()
+        if self.step_logits is not None:
+            self.step_logits.zero_()
+
+
+def check_lookup(num_draft_tokens, max_ngram, B: int = 1, sampling=None, processors=None, constraint=None, return_logprobs: bool = False,
+                 return_hidden: bool = False, kv_cache_dtype: str = "bf16", weight_dtype: str = "bf16",
+                 names=("num_draft_tokens", "max_ngram", "sampling", "processors", "constraint", "return_logprobs", "return_hidden")):
+    """What generate_lookup refuses BY NAME, before any device work (the style of check_processors; names: what the caller's surface calls the
+    arguments).  Prompt-lookup decoding is greedy verification of one sequence on the bf16 path: everything that changes how a token is
+    chosen, or what is recorded per chosen token, would need its own accept kernel."""
+    k_name, n_name, s_name, p_name, c_name, lp_name, h_name = names
+    k, n = int(num_draft_tokens), int(max_ngram)
+    if not 1 <= k <= ops.LOOKUP_MAX_DRAFT:
+        raise ValueError(f"`{k_name}` has to be an integer in 1 .. {ops.LOOKUP_MAX_DRAFT} (a verify step runs {k_name} + 1 <= 16 rows), but is {num_draft_tokens}")
+    if n < 1:                                                  # HF: PromptLookupCandidateGenerator - "Invalid max_matching_ngram_size or num_output_tokens"
+        raise ValueError(f"`{n_name}` has to be a strictly positive integer, but is {max_ngram}")
+    if B != 1:
+        raise NotImplementedError(f"{k_name} with a batch of {B} rows: prompt-lookup decoding verifies the drafts of ONE sequence per step (HF's assisted "
+                                  "generation is batch-size 1 as well; the decode layout has one append slot for all rows)")
+    if sampling is not None:
+        raise NotImplementedError(f"{k_name} with {s_name}: the drafts are verified against the greedy choice (sample-mode speculative decoding needs "
+                                  "rejection sampling, which crab_lookup_accept does not do)")
+    if normalize_processors(processors) is not None:
+        raise NotImplementedError(f"{k_name} with {p_name}: crab_lookup_accept chooses from the raw logits of k + 1 positions at once; the repetition "
+                                  "penalty, n-gram ban and further stop ids edit one position per step (crab_logits_edit)")
+    if constraint is not None:
+        raise NotImplementedError(f"{k_name} with {c_name}: a token trie is walked one edge per step (crab_constrained_select)")
+    if return_logprobs:
+        raise NotImplementedError(f"{k_name} with {lp_name}: the log-probability planes are filled one token per step (crab_logprob_norm / crab_logprob_gather)")
+    if return_hidden:
+        raise NotImplementedError(f"{k_name} with {h_name}: the hidden rows are kept one per step")
+    if kv_cache_dtype == "fp8_e4m3":
+        raise NotImplementedError(f'{k_name} with kv_cache_dtype="fp8_e4m3": crab_attn_verify attends the bf16 cache (the fp8 cache takes one-row decode steps only)')
+    if weight_dtype == "fp8_e4m3":
+        raise NotImplementedError(f'{k_name} with weight_dtype="fp8_e4m3": the verify step runs on the bf16 weights')
+    return k, n
 
 
 class _Constraint:

@@ -1048,6 +1048,76 @@ def attn_own_merge(q, ws, k_cache, v_cache, o, B: int, Sq: int, H: int, Hk: int,
     return o
 
 
+LOOKUP_MAX_DRAFT = 15           # draft tokens of one verify step: k + 1 <= 16 rows (crab_attn_verify's Sq, the M <= 16 projection kernels)
+
+
+def attn_verify(qkv, k_cache, v_cache, o, B: int, Sq: int, H: int, Hk: int, head_dim: int, Tmax: int, ctx_len: int, scale: float,
+                ctx_dev=None, kv_start=None):
+    """crab_attn_verify: query i of sequence b (row b * Sq + i of qkv / o; rotated, its key appended already) over the cache slots
+    kv_start[b] .. ctx_len (+ ctx_dev[0]) - 1 + i -> o [B * Sq, ldo] bf16.  Sq <= 16; every K / V row is read once per (sequence, kv head,
+    group of 16 // (H // Hk) queries)."""
+    d = _dev(qkv)
+    _chk_bf16(qkv, k_cache, v_cache, o)
+    if not (k_cache.is_contiguous() and v_cache.is_contiguous()) or tuple(k_cache.shape) != (B, Hk, Tmax, head_dim) or v_cache.shape != k_cache.shape:
+        raise ValueError("attn_verify: k_cache / v_cache must be contiguous [B, Hk, Tmax, d] tensors")
+    if qkv.dim() != 2 or qkv.stride(1) != 1 or qkv.shape[0] < B * Sq or qkv.shape[1] < H * head_dim:
+        raise ValueError(f"attn_verify: qkv must be a [>= {B * Sq}, >= {H * head_dim}] matrix with contiguous rows, got {tuple(qkv.shape)}")
+    if o.dim() != 2 or o.stride(1) != 1 or o.shape[0] < B * Sq or o.shape[1] < H * head_dim or o.device != qkv.device:
+        raise ValueError("attn_verify: o needs B * Sq rows of H * d contiguous columns on qkv's device")
+    _chk_i32("kv_start", kv_start, B, qkv.device)
+    _chk_i32("ctx_dev", ctx_dev, 1, qkv.device)
+    _lib.check(_lib.load().crab_attn_verify(_lib.ctx(d), _stream(), _p(qkv), qkv.stride(0), _p(k_cache), _p(v_cache), _p(o), o.stride(0), B, Sq, H, Hk,
+                                            head_dim, Tmax, ctx_len, _p(ctx_dev), scale, _p(kv_start)), d)
+    return o
+
+
+def _chk_i64(name: str, t, n: int, device):
+    if t is None or t.dtype != torch.int64 or t.dim() != 1 or t.shape[0] < n or not t.is_contiguous() or t.device != device:
+        raise ValueError(f"{name} must be a contiguous int64 [{n}] tensor on {device}")
+
+
+def lookup_draft(hist, S: int, step_dev, cur_ids, k: int, max_ngram: int, eos_id: int, pad_id: int, max_new_tokens: int, V: int, ids_out,
+                 n_draft, finished):
+    """crab_lookup_draft: the prompt-lookup draft of one verify step (HF PromptLookupCandidateGenerator.get_candidates) from hist int32
+    [S + max_new_tokens] (live length S + step_dev[0]) -> ids_out int64 [k + 1] (current token, drafts, pad), n_draft int32 [1]."""
+    d = _dev(hist)
+    dev = hist.device
+    for nm, t, n in (("hist", hist, S + max_new_tokens), ("step_dev", step_dev, 1), ("n_draft", n_draft, 1), ("finished", finished, 1)):
+        if t is None:
+            raise ValueError(f"lookup_draft: {nm} is required")
+        _chk_i32(nm, t, n, dev)
+    _chk_i64("cur_ids", cur_ids, 1, dev)
+    _chk_i64("ids_out", ids_out, k + 1, dev)
+    _lib.check(_lib.load().crab_lookup_draft(_lib.ctx(d), _stream(), _p(hist), int(S), _p(step_dev), _p(cur_ids), int(k), int(max_ngram), int(eos_id),
+                                             int(pad_id), int(max_new_tokens), int(V), _p(ids_out), _p(n_draft), _p(finished)), d)
+
+
+def lookup_accept(logits, ids, n_draft, cur_ids, out_ids, hist, S: int, pos_dev, step_dev, finished, eos_id: int, pad_id: int, min_new_tokens: int,
+                  max_new_tokens: int, stats, step_logits=None):
+    """crab_lookup_accept: greedy verification of the drafts in ids int64 [k + 1] against logits fp32 [k + 1, V]; emits 1 .. k + 1 tokens into
+    out_ids int64 [max_new_tokens] / hist, advances pos_dev / step_dev, accumulates stats int32 [4] (steps, proposed, accepted, emitted) and, with
+    step_logits fp32 [max_new_tokens, V], keeps the emitted tokens' logits rows."""
+    d = _dev(logits)
+    dev = logits.device
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("lookup_accept: logits must be an fp32 [k + 1, V] matrix with contiguous rows")
+    k, V = logits.shape[0] - 1, logits.shape[1]
+    for nm, t, n in (("n_draft", n_draft, 1), ("hist", hist, S + max_new_tokens), ("pos_dev", pos_dev, 1), ("step_dev", step_dev, 1),
+                     ("finished", finished, 1), ("stats", stats, 4)):
+        if t is None:
+            raise ValueError(f"lookup_accept: {nm} is required")
+        _chk_i32(nm, t, n, dev)
+    _chk_i64("ids", ids, k + 1, dev)
+    _chk_i64("cur_ids", cur_ids, 1, dev)
+    _chk_i64("out_ids", out_ids.reshape(-1) if out_ids is not None and out_ids.is_contiguous() else out_ids, max_new_tokens, dev)
+    if step_logits is not None and (step_logits.dtype != torch.float32 or not step_logits.is_contiguous() or tuple(step_logits.shape) != (max_new_tokens, V)
+                                    or step_logits.device != dev):
+        raise ValueError(f"lookup_accept: step_logits must be a contiguous fp32 [{max_new_tokens}, {V}] tensor on {dev}")
+    _lib.check(_lib.load().crab_lookup_accept(_lib.ctx(d), _stream(), _p(logits), logits.stride(0), V, k, _p(ids), _p(n_draft), _p(cur_ids), _p(out_ids),
+                                              _p(hist), int(S), _p(pos_dev), _p(step_dev), _p(finished), int(eos_id), int(pad_id), int(min_new_tokens),
+                                              int(max_new_tokens), _p(stats), _p(step_logits)), d)
+
+
 def lm_head_xent_bytes(M: int, N: int) -> int:
     return int(_lib.load().crab_lm_head_xent_workspace(int(M), int(N)))
 

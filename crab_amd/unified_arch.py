@@ -191,16 +191,19 @@ class UnifiedMetaForCausalLM:
         batch_task_names=None,
         return_multi_scale_features=False,
         return_gt_mask=False,
+        return_row_token_ids=False,
     ):
         """unified_arch.py:217-406.  Returns the same dict: input_ids=None, inputs_embeds [bs,S,D], attention_mask,
         labels, position_ids (+ multi_scale_image_features, mask_token_mask, gt_mask on the AVS path).
+        return_row_token_ids (generate(prompt_lookup_num_tokens=k) alone asks for it): the dict gains 'row_token_ids', a host int64 [bs, S]
+        tensor with the text token id behind every row and -1 for every row that is none - a spliced modality block, the left padding.
         The AVS `<image>` is encoded ONCE (the reference encodes it twice, :244 and :297)."""
         return self.prepare_multimodal_inputs_many(
             [{"batch_input_ids": batch_input_ids, "batch_labels": batch_labels, "batch_X_modals": batch_X_modals,
               "batch_task_names": batch_task_names}],
-            return_multi_scale_features=return_multi_scale_features, return_gt_mask=return_gt_mask)[0]
+            return_multi_scale_features=return_multi_scale_features, return_gt_mask=return_gt_mask, return_row_token_ids=return_row_token_ids)[0]
 
-    def prepare_multimodal_inputs_many(self, batches, return_multi_scale_features=False, return_gt_mask=False):
+    def prepare_multimodal_inputs_many(self, batches, return_multi_scale_features=False, return_gt_mask=False, return_row_token_ids=False):
         """prepare_multimodal_inputs for SEVERAL collated batches of the eval loop at once (scripts/finetune/inference_hyper_lora.py:1466-1479
         calls generate() once per batch of 8): every batch keeps its own splice, left padding, attention_mask and position_ids - the dict a
         separate call returns - but the <video> / <audio> blocks of ALL batches go through the encoders together (_encode_blocks: equal shapes
@@ -259,11 +262,11 @@ class UnifiedMetaForCausalLM:
         afeat, _ = self._encode_blocks(auds, video=False)
         mids = [self.encode_mask(m, batch_first=False) for m in msks]
         return [self._assemble_inputs(bt, bs, ids_ls, lab_ls, plans, vfeat, vvit, afeat, mids, key_ids, emb_w, D, device,
-                                      return_multi_scale_features, return_gt_mask)
+                                      return_multi_scale_features, return_gt_mask, return_row_token_ids)
                 for (bt, bs, ids_ls, lab_ls, plans) in recs]
 
     def _assemble_inputs(self, bt, bs, ids_ls, lab_ls, plans, vfeat, vvit, afeat, mids, key_ids, emb_w, D, device,
-                         return_multi_scale_features, return_gt_mask):
+                         return_multi_scale_features, return_gt_mask, return_row_token_ids=False):
         """Pass 2 of prepare_multimodal_inputs for ONE batch: lengths, left padding, the spliced output buffer, mask / labels / positions."""
         special = self.SPECIAL_TOKEN_2_IDS
         batch_X_modals, batch_task_names = bt["batch_X_modals"], bt.get("batch_task_names")
@@ -325,6 +328,12 @@ class UnifiedMetaForCausalLM:
             'labels': labels.to(device),
             'position_ids': position_ids.to(device),
         }
+        if return_row_token_ids:
+            # the history of prompt-lookup decoding: the text token id behind every row, -1 where a modality block was spliced in and on the left padding
+            rows = torch.from_numpy(tok.copy())
+            for i in range(bs):
+                rows[i, :S - lens[i]] = -1
+            dict_data['row_token_ids'] = rows
         if return_multi_scale_features:
             scale = 2
             ms = [[] for _ in range(scale)]

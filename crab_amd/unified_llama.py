@@ -314,7 +314,16 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
         current distribution.  None and 0 are off (all three off: the plain sampling call, launch for launch); without do_sample they have
         no effect, as in HF.  Also in generate_batches / generate_questions / generate_avs*, and with guidance_scale (the guided scores go
         through them).  A value out of range or NaN raises ValueError by name (HF drops a cutoff outside (0, 1) silently);
-        allowed_sequences with a live one is refused by name; typical_p stays refused."""
+        allowed_sequences with a live one is refused by name; typical_p stays refused.
+        prompt_lookup_num_tokens = k (1 .. 15), max_matching_ngram_size = n (default 2, HF's): prompt-lookup speculative decoding
+        (GenerationEngine.generate_lookup; csrc/lookup.hip, csrc/attn_verify.hip) - every step drafts up to k tokens from the sequence's own
+        token history and verifies them in one pass over the weights.  Greedy, one row.  The history is batch_input_ids with -1 at the rows
+        a modality embedding was spliced into; with inputs_embeds alone it starts empty, as HF's does.  The ids are generate()'s own under the
+        decoder's bf16 margin rule; output_logits + return_dict_in_generate gives the logits of the emitted tokens.  Refused by name next to
+        it: do_sample, num_beams > 1, guidance_scale, allowed_sequences, repetition_penalty / no_repeat_ngram_size, output_token_logprobs, a
+        batch of more than one row; assistant_model stays refused."""
+        if kwargs.get("prompt_lookup_num_tokens") is not None:
+            return UnifiedForCausalLM._generate_lookup(self, batch_input_ids, batch_labels, batch_X_modals, batch_task_names, kwargs)
         beams =int(kwargs.get("num_beams") or 1)
         # _GUIDANCE_ARGS and _WARPER_ARGS are read from the class: generate() alone routes guidance_scale, and _sampling parses the warpers, whatever
         # object stands in for self
@@ -413,6 +422,65 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
         out.sequences, sl = res
         sl = sl[: out.sequences.shape[0]]                      # the raw logits of the conditional rows
         out.logits = tuple(sl[:, i] for i in range(sl.shape[1]))
+        return out
+
+    def _generate_lookup(self, batch_input_ids, batch_labels, batch_X_modals, batch_task_names, kwargs):
+        """generate(prompt_lookup_num_tokens = k): prompt-lookup speculative decoding through GenerationEngine.generate_lookup.  What it does not
+        combine with is refused by name before any device work."""
+        from .decoder import check_lookup
+        k = kwargs["prompt_lookup_num_tokens"]
+        neutral = {"do_sample": False, "num_beams": 1, "guidance_scale": 1.0, "allowed_sequences": None, "allowed_set": None, "repetition_penalty": 1.0,
+                   "no_repeat_ngram_size": 0, "output_token_logprobs": False}
+        for name, off in neutral.items():
+            v = kwargs.get(name)
+            if v is None or v == off or (isinstance(off, bool) and not v):
+                continue
+            raise NotImplementedError(f"generate(prompt_lookup_num_tokens={k}, {name}={v!r}): not implemented with prompt lookup (greedy decoding of one "
+                                      "row with min_new_tokens, one eos_token_id and output_logits is)")
+        # the names checked above are neutral here; the warpers have no effect on a greedy call (as in generate())
+        UnifiedForCausalLM._check_generate_kwargs(kwargs, UnifiedForCausalLM._LOOKUP_ARGS | UnifiedForCausalLM._PROCESSOR_ARGS | UnifiedForCausalLM._GUIDANCE_ARGS |
+                                                  UnifiedForCausalLM._WARPER_ARGS | {"num_beams"})
+        eos = kwargs.get("eos_token_id", self.config.eos_token_id)
+        if torch.is_tensor(eos):
+            eos = eos.reshape(-1).tolist()
+        if isinstance(eos, (list, tuple)):
+            ids = list(dict.fromkeys(int(e) for e in eos))
+            if len(ids) > 1:
+                raise NotImplementedError(f"generate(prompt_lookup_num_tokens={k}, eos_token_id={ids}): a prompt-lookup call stops on ONE eos_token_id")
+            eos = ids[0] if ids else None
+        embeds = kwargs.pop("inputs_embeds", None)
+        rows = int(embeds.shape[0]) if embeds is not None else len(batch_input_ids)
+        mm = kwargs.get("max_matching_ngram_size")
+        k, n = check_lookup(k, 2 if mm is None else mm, rows, kv_cache_dtype=kwargs.get("kv_cache_dtype") or self._engine.kv_cache_dtype,
+                            weight_dtype=kwargs.get("weight_dtype") or self._engine.weight_dtype,
+                            names=("prompt_lookup_num_tokens", "max_matching_ngram_size", "do_sample", "repetition_penalty / no_repeat_ngram_size",
+                                   "allowed_sequences", "output_token_logprobs", "return_hidden"))
+        prompt_ids = None
+        if embeds is None:
+            inputs = self.prepare_multimodal_inputs(batch_input_ids=batch_input_ids, batch_labels=batch_labels, batch_X_modals=batch_X_modals,
+                                                    return_multi_scale_features=False, return_gt_mask=False, batch_task_names=batch_task_names,
+                                                    return_row_token_ids=True)
+            embeds = inputs['inputs_embeds']
+            prompt_ids = inputs['row_token_ids'][0]            # -1 at the rows of a spliced modality block
+        embeds = embeds.to(device=self.device, dtype=BF16)
+        pad = kwargs.get("pad_token_id", self.model.pad_token_id if self.model.pad_token_id is not None else eos)
+        want_logits = bool(kwargs.get("output_logits")) and bool(kwargs.get("return_dict_in_generate"))
+        want_first = bool(kwargs.get("output_first_logits"))
+        res = self._engine.generate_lookup(embeds, int(kwargs.get("max_new_tokens", 20)), k, n, prompt_ids=prompt_ids, eos_token_id=eos, pad_token_id=pad,
+                                           min_new_tokens=int(kwargs.get("min_new_tokens", 0) or 0), use_graph=kwargs.get("use_graph", True),
+                                           return_step_logits=want_logits, return_first_logits=want_first, return_stats=True,
+                                           kv_cache_dtype=kwargs.get("kv_cache_dtype"), weight_dtype=kwargs.get("weight_dtype"))
+        res = list(res)
+        self.last_lookup = {"stats": res.pop(), "prompt_ids": prompt_ids}      # the counters and the history the engine was given, for audits
+        if not (want_logits or want_first):
+            return res[0]
+        out = type("GenerateOutput", (), {})()
+        out.sequences = res.pop(0)
+        if want_logits:
+            sl = res.pop(0)
+            out.logits = tuple(sl[:, i] for i in range(sl.shape[1]))
+        if want_first:
+            out.first_logits = res.pop(0)
         return out
 
     def _generate_beam(self, batch_input_ids, batch_labels, batch_X_modals, batch_task_names, kwargs):
@@ -561,7 +629,7 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
                     "logits_processor": None, "stopping_criteria": None, "prefix_allowed_tokens_fn": None, "constraints": None, "typical_p": 1.0,
                     "epsilon_cutoff": 0.0, "eta_cutoff": 0.0, "diversity_penalty": 0.0, "suppress_tokens": None, "begin_suppress_tokens": None,
                     "forced_bos_token_id": None, "forced_eos_token_id": None, "assistant_model": None, "streamer": None, "max_time": None,
-                    "stop_strings": None, "min_p": None, "guidance_scale": None, "sequence_bias": None}
+                    "stop_strings": None, "min_p": None, "guidance_scale": None, "sequence_bias": None, "prompt_lookup_num_tokens": None}
 
     # the names of _UNSUPPORTED that the decode step implements (csrc/logits_proc.hip): an entry point that routes them to the engine says so
     _PROCESSOR_ARGS = frozenset(("repetition_penalty", "no_repeat_ngram_size"))
@@ -569,6 +637,8 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
     _BEAM_ARGS = frozenset(("num_beams", "length_penalty", "num_return_sequences"))
     # the name of _UNSUPPORTED that generate(guidance_scale > 1) hands to GenerationEngine.generate_guided (csrc/cfg.hip); generate() alone passes it
     _GUIDANCE_ARGS = frozenset(("guidance_scale",))
+    # the name of _UNSUPPORTED that generate(prompt_lookup_num_tokens = k) hands to GenerationEngine.generate_lookup (csrc/lookup.hip); generate() alone passes it
+    _LOOKUP_ARGS = frozenset(("prompt_lookup_num_tokens",))
     # the names of _UNSUPPORTED that _sampling parses (csrc/sample_warp.hip): every entry point that takes do_sample through _sampling passes them
     _WARPER_ARGS = frozenset(("min_p", "epsilon_cutoff", "eta_cutoff"))
 

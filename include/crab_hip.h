@@ -564,6 +564,54 @@ int crab_cfg_mix(crab_ctx* ctx, void* stream, const float* logits, int64_t ldl, 
 int crab_cfg_follow(crab_ctx* ctx, void* stream, int64_t* cur_ids, int64_t* out_ids, int64_t ld_out, int n_steps, int32_t* finished,
                     const int32_t* step_dev, int B);
 
+/* ---- Prompt-lookup speculative decoding (HF generate(prompt_lookup_num_tokens = k, max_matching_ngram_size = n), batch size 1, greedy): one
+ * VERIFY step runs the model on [current token ; k draft tokens] of one sequence and emits 1 .. k + 1 tokens for one read of the weights.
+ * Device-resident and capturable: draft -> embedding -> layers (S = k + 1) -> lm_head -> accept, no host round trip.
+ *
+ * crab_attn_verify (csrc/attn_verify.hip): the attention of that step (modeling_llama.py:394-445 under the causal mask of the k + 1 new
+ * positions).  Query i (0 .. Sq - 1) of sequence b is row b * Sq + i of qkv (head h at column h * d, rotated already; the new keys appended
+ * already - crab_qkv_rope_split with S = Sq and the device position word) and of o (bf16 [B * Sq, ldo]); it attends the slots
+ * max(kv_start[b], 0) .. ctx - 1 + i of k_cache / v_cache [B, Hk, Tmax, d], ctx = ctx_len_host + ctx_dev[0] (ctx_dev NULL: the host value
+ * alone; kv_start NULL = 0), never past Tmax - crab_attn_own_merge's convention.  The queries of a sequence are matrix-instruction operand
+ * rows: one block per (sequence, kv head, group of 16 / (H / Hk) queries), every K / V row up to the group's last visible slot is read once
+ * per block.  A slot past a query's limit contributes an exact zero to it, whatever it holds; slots no query of a group sees are not read.
+ * No atomics, fixed merge order.  d = 64 / 128 with H / Hk in {1, 2, 4, 7, 8} and 1 <= Sq <= 16, CRAB_E_UNSUPPORTED otherwise;
+ * CRAB_E_INVALID for null operands, ctx_len out of range, ldqkv % 8, ldqkv / ldo < H * d, pointers not 16-byte aligned.
+ *
+ * crab_lookup_draft (csrc/lookup.hip; candidate_generator.py PromptLookupCandidateGenerator.get_candidates): hist int32 [S + max_new_tokens]
+ * holds the prompt's ids row by row (-1: no text token) and then the emitted tokens; len = S + step_dev[0].  For n = min(max_ngram, len - 1)
+ * down to 1, the match positions idx (hist[idx .. idx + n) equal to the last n entries, idx + n < len) in ascending order: the first whose
+ * continuation hist[idx + n .. min(idx + n + k, len)) does not begin with a "no token" entry (-1 or outside [0, V); such an entry equals
+ * nothing, itself included) is chosen - HF's "for idx in match_indices ... if start_idx < end_idx", with its crop-and-continue of forbidden
+ * tokens in the place of -1.  The draft is that continuation cut at the first "no token" entry, to max_new_tokens - step - 1 entries (the
+ * verify step adds one token itself; HF: "if self.max_length == input_length + 1: return") and before the first eos_id (HF: "chosen_ids =
+ * chosen_ids[:first_eos_index]" after match_found is set: an EOS crop that leaves nothing ends the search with no draft).
+ * ids_out int64 [k + 1]: cur_ids[0], the n_draft draft tokens, pad_id behind them; n_draft_dev[0] = n_draft (0 .. k).  finished[0] != 0:
+ * n_draft = 0 and ids_out is left alone.
+ *
+ * crab_lookup_accept (generation/utils.py _assisted_decoding, greedy: "n_matches = ((~(candidate_new_tokens == selected_tokens[:, :-1]))
+ * .cumsum(dim=-1) < 1).sum()", then "valid_tokens = selected_tokens[:, : n_matches + 1]"): logits fp32 [k + 1, V] (row stride ldl), row i
+ * the model's answer after ids[i].  t_i = first maximum of row i (crab_greedy_select's rule; eos_id suppressed while step + i <
+ * min_new_tokens), a = the leading i < n_draft with t_i == ids[i + 1].  t_0 .. t_a go to out_ids[step ..] and hist[S + step ..], cut after the
+ * first eos_id and at max_new_tokens - either sets finished[0]; cur_ids[0] = the last emitted token; pos_dev[0] and step_dev[0] advance by
+ * the number emitted.  step_logits_out (fp32 [max_new_tokens, V], may be NULL) receives the logits rows of the emitted tokens at rows
+ * step ...  stats int32 [4] accumulates: verify steps run while unfinished, drafts proposed, drafts accepted, tokens emitted.
+ * finished[0] != 0 on entry: nothing is written.  Rejected drafts need no rollback: their K / V rows lie above the new position, no query
+ * sees them (crab_attn_verify's limit) and the next step's k + 1 appended rows overwrite them.
+ * Both: one block, every index read from device memory clamped against the launch's sizes; CRAB_E_INVALID for null operands, k outside
+ * 1 .. 15, max_ngram < 1, a pad_id outside [0, V), ldl < V.
+ * ADDED under ABI 13 (crab_abi_version() still returns 13: nothing that existed changed); probe for the symbol, not for a version number. */
+int crab_attn_verify(crab_ctx* ctx, void* stream, const void* qkv, int64_t ldqkv, const void* k_cache, const void* v_cache, void* o,
+                     int64_t ldo, int B, int Sq, int H, int Hk, int d, int Tmax, int ctx_len_host, const int32_t* ctx_dev, float scale,
+                     const int32_t* kv_start);
+int crab_lookup_draft(crab_ctx* ctx, void* stream, const int32_t* hist, int S, const int32_t* step_dev, const int64_t* cur_ids, int k,
+                      int max_ngram, int eos_id, int pad_id, int max_new_tokens, int V, int64_t* ids_out, int32_t* n_draft_dev,
+                      const int32_t* finished);
+int crab_lookup_accept(crab_ctx* ctx, void* stream, const float* logits, int64_t ldl, int V, int k, const int64_t* ids,
+                       const int32_t* n_draft_dev, int64_t* cur_ids, int64_t* out_ids, int32_t* hist, int S, int32_t* pos_dev,
+                       int32_t* step_dev, int32_t* finished, int eos_id, int pad_id, int min_new_tokens, int max_new_tokens,
+                       int32_t* stats, float* step_logits_out);
+
 /* ---------------------------------------------------------------------------------------------
  * Teacher-forced scoring (csrc/xent.hip): the language-model loss of models/modeling_llama.py:1261-1274 as reached from
  * models/unified_llama.py:129-160 - logits.float(), shift by one, CrossEntropyLoss(ignore_index = -100) - without the logits.
