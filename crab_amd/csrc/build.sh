@@ -8,9 +8,11 @@ OUT=../libcrab_hip.so
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result -mllvm -pragma-unroll-threshold=200000"
 mkdir -p build
 pids=()
+objs=()
 for f in *.hip; do
   o=build/${f%.hip}.o
-  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ common.h -nt "$o" ] || [ crab_internal.h -nt "$o" ] || [ fp8_common.h -nt "$o" ] || [ gemm_epilogue.h -nt "$o" ] || [ attn_decode_core.h -nt "$o" ] || [ build.sh -nt "$o" ] || [ ../../include/crab_hip.h -nt "$o" ]; then
+  objs+=("$o")
+  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ common.h -nt "$o" ] || [ crab_internal.h -nt "$o" ] || [ fp8_common.h -nt "$o" ] || [ gemm_epilogue.h -nt "$o" ] || [ attn_decode_core.h -nt "$o" ] || [ attn_rows_core.h -nt "$o" ] || [ select_core.h -nt "$o" ] || [ build.sh -nt "$o" ] || [ ../../include/crab_hip.h -nt "$o" ]; then
     extra=""
     # attn.hip: keep the MFMA accumulators in VGPRs.  The flash kernels rescale O every K/V tile; with AGPR accumulators that is
     # 32 v_accvgpr_read + 32 v_mov around 32 multiplies per tile (CLIP shape 150 -> 126 us, decoder shape 217 -> 213 us)
@@ -21,5 +23,5 @@ for f in *.hip; do
   fi
 done
 for p in "${pids[@]}"; do wait "$p"; done
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC build/*.o -o "$OUT" -ldl
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC "${objs[@]}" -o "$OUT" -ldl
 echo "built $(realpath $OUT)"

@@ -7,33 +7,19 @@
 //   * greedy   : greedy_select_kernel's rule over edge indices (larger value wins, on equal values the lower edge = the lower token id);
 //   * sampling : sample_select_kernel's algorithm with the edge index in the place of the token index - the same 1024-way partition
 //                (chunk = ceil(n / 1024)), the same bisections, the same fixed-order block_sum and the same generator, so a node whose edges
-//                are all V tokens in order draws exactly what crab_sample_select draws.
+//                are all V tokens in order draws exactly what crab_sample_select draws.  fkey and block_sum are select_core.h's; the
+//                pipeline is a copy of select_draw, not an instantiation: as one (bit-identical, scripts/ab_bits.py select) the kernel
+//                needed 52 registers instead of 70, two blocks fitted a CU, and 512 rows on a 1000-edge node took 324 us instead of 254
+//                (V = 32000) and 585 instead of 340 (V = 152064); held to one block per CU it was still 7 - 15 % slower at 1, 42 and 1000
+//                edges (scripts/bench_constrained.py, parent-to-parent spread under 1 %).
 // Every index taken from device memory is clamped against the sizes the launch was given (node against n_nodes, the edge range against
 // n_edges, edge_tok against V): a bad entry is "not allowed", a corrupt array gives a wrong token and never an out-of-bounds access.
 #include "common.h"
 #include "crab_internal.h"
+#include "select_core.h"
 #include <math.h>
 
 namespace {
-
-__device__ __forceinline__ uint32_t fkey(float f) {            // order-preserving float -> uint (as sample.hip)
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-template <typename T>
-__device__ __forceinline__ T block_sum(T v, T* sh) {            // 1024 threads, fixed tree: deterministic (as sample.hip)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    __syncthreads();
-    if (lane == 0) sh[wave] = v;
-    __syncthreads();
-    T t = sh[0];
-#pragma unroll
-    for (int w = 1; w < 16; ++w) t += sh[w];
-    return t;
-}
 
 // edge i of the row's node: allowed iff its token lies in [0, V) and is not the suppressed EOS
 __device__ __forceinline__ bool edge_ok(const int* __restrict__ etok, int i, int V, int suppress, int* tok) {

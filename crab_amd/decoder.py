@@ -236,7 +236,7 @@ def check_processors(processors, min_new_tokens: int = 0, constrained: bool = Fa
 
 def normalize_sampling(sampling, constrained: bool = False):
     """The `sampling` argument of the generate entry points: None (greedy), (temperature, top_k, top_p, seed) or, with HF's further truncation
-    warpers, (temperature, top_k, top_p, seed, min_p, epsilon_cutoff, eta_cutoff) - 0 or None = that stage is off (csrc/sample_warp.hip).
+    warpers, (temperature, top_k, top_p, seed, min_p, epsilon_cutoff, eta_cutoff) - 0 or None = that stage is off (csrc/sample.hip).
     A 7-tuple whose three stages are all off comes back as the 4-tuple: that call is the plain sampling call (same state key, same graph,
     same launches).  Values outside min_p in [0, 1] / the cutoffs in [0, 1), NaN included, raise ValueError by name; a live stage with a
     token trie (constrained) is refused by name - crab_constrained_select is a kernel of its own.  All before any device work."""
@@ -1199,7 +1199,7 @@ class GenerationEngine:
             t, k, p_, seed = st.sampling
             ops.sample_select(logits, st.cur_ids, st.out_ids, st.step_dev, st.finished, st.eos, st.pad, st.min_new, t, k, p_, seed + 7919 * st.slot)
         else:
-            # a live min_p / epsilon_cutoff / eta_cutoff (normalize_sampling: a 7-tuple holds at least one): csrc/sample_warp.hip
+            # a live min_p / epsilon_cutoff / eta_cutoff (normalize_sampling: a 7-tuple holds at least one): csrc/sample.hip
             t, k, p_, seed, min_p, eps, eta = st.sampling
             ops.sample_select_warped(logits, st.cur_ids, st.out_ids, st.step_dev, st.finished, st.eos, st.pad, st.min_new, t, k, p_,
                                      seed + 7919 * st.slot, min_p, eps, eta)

@@ -679,7 +679,7 @@ def sample_select(logits, cur_ids, out_ids, step_dev, finished, eos_id: int, pad
 
 def sample_select_warped(logits, cur_ids, out_ids, step_dev, finished, eos_id: int, pad_id: int, min_new_tokens: int, temperature: float, top_k: int,
                          top_p: float, seed: int, min_p: float = 0.0, epsilon_cutoff: float = 0.0, eta_cutoff: float = 0.0, kept_n=None, kept_min=None):
-    """crab_sample_select_warped (csrc/sample_warp.hip): sample_select with HF's min_p -> epsilon_cutoff -> eta_cutoff stages between top-p and
+    """crab_sample_select_warped (csrc/sample.hip): sample_select with HF's min_p -> epsilon_cutoff -> eta_cutoff stages between top-p and
     the draw (0 = that stage is off; all three off gives sample_select's ids bit for bit).  logits [B, V] fp32 rows with unit column stride
     (a row stride of 0 - one row expanded - is fine: the rows are only read); cur_ids int64 [>= B], out_ids int64 [B, n_steps] with unit
     column stride, step_dev int32 [1], finished int32 [>= B].  kept_n (int32 [>= B]) / kept_min (fp32 [>= B]), each optional: the size of

@@ -309,7 +309,7 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
         below 1.  A token that is -inf in either row scores -inf (HF: NaN where both are).
         min_p / epsilon_cutoff / eta_cutoff (with do_sample): HF's MinPLogitsWarper, EpsilonLogitsWarper and EtaLogitsWarper, in HF's order
         after temperature, top_k and top_p - every stage on the distribution renormalised over what the stages before it kept, the largest
-        token and its ties always kept (csrc/sample_warp.hip, inside the decode step).  min_p in (0, 1] removes p_i < min_p * p_max;
+        token and its ties always kept (csrc/sample.hip, inside the decode step).  min_p in (0, 1] removes p_i < min_p * p_max;
         epsilon_cutoff in (0, 1) removes p_i < eps; eta_cutoff in (0, 1) removes p_i < min(eps, sqrt(eps) * exp(-H)), H the entropy of the
         current distribution.  None and 0 are off (all three off: the plain sampling call, launch for launch); without do_sample they have
         no effect, as in HF.  Also in generate_batches / generate_questions / generate_avs*, and with guidance_scale (the guided scores go
@@ -639,7 +639,7 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
     _GUIDANCE_ARGS = frozenset(("guidance_scale",))
     # the name of _UNSUPPORTED that generate(prompt_lookup_num_tokens = k) hands to GenerationEngine.generate_lookup (csrc/lookup.hip); generate() alone passes it
     _LOOKUP_ARGS = frozenset(("prompt_lookup_num_tokens",))
-    # the names of _UNSUPPORTED that _sampling parses (csrc/sample_warp.hip): every entry point that takes do_sample through _sampling passes them
+    # the names of _UNSUPPORTED that _sampling parses (csrc/sample.hip): every entry point that takes do_sample through _sampling passes them
     _WARPER_ARGS = frozenset(("min_p", "epsilon_cutoff", "eta_cutoff"))
 
     @classmethod
@@ -691,7 +691,7 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
     def _sampling(kwargs):
         """HF sample-mode arguments -> (temperature, top_k, top_p, seed) or None (greedy).  Defaults = what a Llama-2-chat checkpoint's
         generation_config + GenerationConfig's own defaults give the reference's generate() call (temperature 0.6, top_p 0.9, top_k 50).
-        min_p / epsilon_cutoff / eta_cutoff (_WARPER_ARGS; HF's MinP-, Epsilon- and EtaLogitsWarper, csrc/sample_warp.hip) are parsed and
+        min_p / epsilon_cutoff / eta_cutoff (_WARPER_ARGS; HF's MinP-, Epsilon- and EtaLogitsWarper, csrc/sample.hip) are parsed and
         validated here - this is the one function every entry point that samples goes through: a live one makes the result the 7-tuple
         (temperature, top_k, top_p, seed, min_p, epsilon_cutoff, eta_cutoff)."""
         warp = []

@@ -416,7 +416,7 @@ int crab_advance(crab_ctx* ctx, void* stream, int32_t* pos_dev, int32_t* step_de
 int crab_sample_select(crab_ctx* ctx, void* stream, const float* logits, int64_t ldl, int B, int V, int64_t* cur_ids,
                        int64_t* out_ids, int64_t ld_out, const int32_t* step_dev, int32_t* finished, int eos_id, int pad_id,
                        int min_new_tokens, float temperature, int top_k, float top_p, uint64_t seed);
-/* crab_sample_select with HF's three further truncation warpers between top-p and the draw (csrc/sample_warp.hip), in HF's order:
+/* crab_sample_select with HF's three further truncation warpers between top-p and the draw (csrc/sample.hip), in HF's order:
  * temperature -> top_k -> top_p -> min_p -> epsilon_cutoff -> eta_cutoff -> draw.  Every stage sees the distribution renormalised over what
  * the stages before it kept, and the largest token with its exact ties always stays (min_tokens_to_keep = 1):
  *   min_p          in [0, 1], 0 = off: removes token i when p_i < min_p * p_max               (MinPLogitsWarper)

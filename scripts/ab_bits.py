@@ -1,11 +1,12 @@
 """Bit-compare two builds of libcrab_hip.so on the decode GEMMs (csrc/skinny.hip and the split-K reduction of csrc/gemm.hip) and on the decode
-attention kernels (csrc/attn_decode_core.h and its users in attn.hip, attn_prefix.hip, kv_fp8.hip).
+attention kernels (csrc/attn_decode_core.h and its users in attn.hip, attn_prefix.hip, kv_fp8.hip; csrc/attn_rows_core.h and its users in
+attn_prefix.hip, attn_verify.hip), and - the list `select`, on request - on the sampling selects (csrc/select_core.h: sample.hip, constrain.hip).
 
-    python scripts/ab_bits.py <a.so> <b.so> [gemm | attn]
+    python scripts/ab_bits.py <a.so> <b.so> [gemm | attn | select]
 
-One fresh child process per library (CRAB_HIP_LIB, crab_amd/_lib.py) runs the launch lists below (both, or the one named) on seeded inputs and
-saves every output tensor; the parent compares the two sets with torch.equal and prints every case that differs.  Exit status 0: every
-case identical.  The attention cases are one or two launches each (edge cases), followed by "volume" cases of 128 x 32 rows per
+One fresh child process per library (CRAB_HIP_LIB, crab_amd/_lib.py) runs the launch lists below (gemm and attn, or the one named) on seeded
+inputs and saves every output tensor; the parent compares the two sets with torch.equal and prints every case that differs.  Exit status 0:
+every case identical.  The attention cases are one or two launches each (edge cases), followed by "volume" cases of 128 x 32 rows per
 launch: the kernels write a * b + c * d, which product gets fused is the compiler's choice per build, and the last fp32 bit this moves reaches
 about one bf16 output in 10^4 - the edge cases alone pass such a build.  Cache rows outside the visible range hold NaN, and outputs are
 compared as bit patterns (a NaN that reaches an output must be the same NaN)."""
@@ -224,6 +225,53 @@ def _attn_cases():
                                                                     wss[b].clone()))
             yield run(f"volume d={d} #{r} fp8", lambda: ops.attn_decode_fp8(qkv, tab, k8[0], v8[0], s8k[0], s8v[0], o(), B, H, H, d, Tmax, ctx, sc, kv_start=ks))
         del kc, vc, k8, v8
+    # ---- attn_verify (px_attend of csrc/attn_rows_core.h with the per-row limit) and the multi-query form of attn_own_merge (the same loop without
+    # it).  G = 1, 4, 7; Sq = 1, 3, 8, 16: both ROWS forms, one to eight query groups.  kv_start > 0; the rows' limits (ctx + i - kv_start) straddle
+    # a 16-key tile edge | the 512-key chunk edge | (ctx = 505) end below the chunk edge for sequence 0 and across it for sequence 1
+    B, Hk, Tmax = 2, 2, 560
+    lo = [3, 9]
+    for d in (64, 128):
+        sc = d ** -0.5
+        for G in (1, 4, 7):
+            H, per = G * Hk, 16 // G
+            for Sq in (1, 3, 8, 16):
+                q = _rand(B * Sq, H * d, seed=110 + d + Sq)
+                for ctx in (3 + 16 - Sq // 2, 3 + 512 - Sq // 2, 505):
+                    kc, vc = cache(B, Hk, Tmax, d, lo, ctx + Sq - 1, seed=111)
+                    yield run(f"verify d={d} G={G} Sq={Sq} ctx={ctx}",
+                              lambda: ops.attn_verify(q, kc, vc, torch.zeros_like(q), B, Sq, H, Hk, d, Tmax, ctx, sc, kv_start=i32(lo)))
+                    if Sq > per:                                            # several query groups: NaN from the FIRST group's last visible slot on
+                        kc, vc = cache(B, Hk, Tmax, d, lo, ctx + per - 1, seed=111)
+                        yield run(f"verify d={d} G={G} Sq={Sq} ctx={ctx} first group",
+                                  lambda: ops.attn_verify(q, kc, vc, torch.zeros_like(q), B, Sq, H, Hk, d, Tmax, ctx, sc,
+                                                          kv_start=i32(lo)).view(B, Sq, H * d)[:, :per].contiguous())
+                # the clamp at Tmax: a device ctx word carries the queries past the cache (the host check sees ctx_len alone)
+                kc, vc = cache(B, Hk, Tmax, d, lo, Tmax, seed=111)
+                yield run(f"verify d={d} G={G} Sq={Sq} clamp at Tmax",
+                          lambda: ops.attn_verify(q, kc, vc, torch.zeros_like(q), B, Sq, H, Hk, d, Tmax, Tmax - Sq - 3, sc, ctx_dev=i32([Sq // 2 + 4]),
+                                                  kv_start=i32(lo)))
+            for Sq in (3, 8):
+                rows, P, Tp = B * Sq, 17, 24
+                q = _rand(rows, H * d, seed=120 + d + Sq)
+                tiles, row_clip = ops.prefix_tile_plan([rows], H, Hk)
+                for ctx in (3 + 16 - Sq // 2, 3 + 512 - Sq // 2):
+                    def multi():
+                        pk, pv = cache(1, Hk, Tp, d, [0], P, seed=81)
+                        ws = torch.zeros(ops.attn_prefix_bytes(rows, H, d), dtype=torch.uint8, device="cuda")
+                        ops.attn_prefix_partial(q, pk, pv, ws, i32(tiles).reshape(-1), i32(row_clip), rows, H, Hk, d, P, sc)
+                        kc, vc = cache(B, Hk, Tmax, d, lo, ctx + Sq - 1, seed=111)
+                        return ops.attn_own_merge(q, ws, kc, vc, torch.zeros_like(q), B, Sq, H, Hk, d, Tmax, ctx, sc, kv_start=i32(lo)), ws
+                    yield run(f"own_merge d={d} G={G} Sq={Sq} ctx={ctx}", multi)
+    for d in (64, 128):                                                     # volume, as above: 64 x 8 (one group of 8 operand rows) and 64 x 16 queries x 32 heads
+        B, H, Tmax, ctx = 64, 32, 152, 130
+        gen = torch.Generator(device="cuda").manual_seed(130 + d)
+        rn = lambda *shape: (torch.randn(*shape, device="cuda", generator=gen) * 0.5).bfloat16()
+        kc, vc = rn(B, H, Tmax, d), rn(B, H, Tmax, d)
+        ks = i32([(7 * b) % 64 for b in range(B)])
+        for Sq in (8, 16):
+            q = rn(B * Sq, H * d)
+            yield run(f"volume d={d} verify Sq={Sq}", lambda: ops.attn_verify(q, kc, vc, torch.zeros_like(q), B, Sq, H, H, d, Tmax, ctx, d ** -0.5, kv_start=ks))
+        del kc, vc
     # ---- attn_decode through attn_decode_gqa_kernel<128, 4>: a control for a file that is recompiled
     B, H, Hk, d, Tmax, ctx = 64, 16, 4, 128, 72, 70
     q = _rand(B, H * d, seed=90)
@@ -232,7 +280,88 @@ def _attn_cases():
     yield run("decode grouped-query G=4", lambda: ops.attn_decode(q, kc, vc, torch.zeros_like(q), B, H, Hk, d, Tmax, ctx, d ** -0.5, kv_start=i32(lo)))
 
 
-LISTS = {"gemm": _cases, "attn": _attn_cases}
+def _select_cases():
+    """Yields (name, tensors) for the sampling selects (csrc/select_core.h): sample_select, sample_select_warped (ids, kept_n, kept_min) and
+    constrained_select (ids, node).  An id moves only when a one-ulp change of a mass crosses the drawn number, so the edge cases are followed by
+    launches of 8192 rows.  Every logits tensor is a view from row 1 of a buffer one row taller: a library that reads in front of a row without a
+    finite token (sample_select_kernel did) stays inside the allocation."""
+    from crab_amd import ops
+
+    def i32(v):
+        return torch.tensor(v, dtype=torch.int32, device="cuda")
+
+    def rows(B, V, seed):
+        g = torch.Generator().manual_seed(seed)
+        buf = torch.randn(B + 1, V, generator=g) * 3
+        if B == 8:
+            buf[2] = 0.5                                                    # exact ties
+            buf[3] = -INF
+            buf[3, V // 2] = 1.25                                           # one finite token
+            buf[4] = -INF                                                   # none
+            buf[5, : V // 2] = buf[5, V - 1]                                # ties at one value among random ones
+        return buf.cuda()[1:]
+
+    def launch(name, B, step, fn, extra=()):
+        """fn(cur, out, step_dev, finished) -> the state after the launch (+ extra tensors)."""
+        cur = torch.full((B,), -7, dtype=torch.int64, device="cuda")
+        out = torch.full((B, 4), -7, dtype=torch.int64, device="cuda")
+        fin = i32([1 if b % 8 in (6, 7) else 0 for b in range(B)])          # rows 6 and 7 of every 8 are finished
+        fn(cur, out, i32([step]), fin)
+        torch.cuda.synchronize()
+        return "select " + name, [_bits(t) for t in (cur, out, fin, *extra)]
+
+    def tries(V, eos):
+        """name -> (edge_off, edge_tok, edge_dst, node) for 8 rows."""
+        ident = ([0, V], list(range(V)), [0] * V, [0] * 8)
+        e0 = sorted(set(range(0, V, 7)) | {eos})
+        e1 = [eos, V - 1, V // 2]
+        off, tok, dst = [0, len(e0), len(e0) + 3, len(e0) + 3], e0 + e1, [1] * len(e0) + [2] * 3
+        sparse = (off, tok, dst, [0, 1, 2, 0, 1, 0, 1, 2])                  # node 2: the sink, no edges
+        btok = list(tok)
+        btok[0], btok[-1], btok[len(btok) // 2] = -5, V + 10, 1 << 30
+        bad = ([0, len(e0), len(tok) + 50, -3], btok, dst, [0, 1, 2, -1, 7, 0, 1, 0])       # edge ranges and nodes out of range too
+        return {"identity": ident, "sparse": sparse, "corrupt": bad}
+
+    INF = float("inf")
+    PAD, MIN_NEW, SEED = 0, 2, 1234
+    WARPS = {"min_p": (0.05, 0.0, 0.0), "epsilon": (0.0, 2e-3, 0.0), "eta": (0.0, 0.0, 5e-3), "all": (0.05, 2e-3, 5e-3)}
+    for V in (1, 1000, 1025, 5000):                                         # one item per thread with idle threads | ragged chunk of 2 | chunk of 5
+        B, eos = 8, min(2, V - 1)
+        lg = rows(B, V, seed=200 + V)
+        trie = {k: tuple(i32(a) for a in v) for k, v in tries(V, eos).items()}
+        for step in (0, 3):                                                 # EOS suppressed | not
+            for name, (off, tok, dst, node) in trie.items():
+                nd = node.clone()
+                yield launch(f"constrained greedy V={V} step={step} {name}", B, step,
+                             lambda c, o, s, f: ops.constrained_select(lg, off, tok, dst, nd, c, o, s, f, eos, PAD, MIN_NEW), (nd,))
+            for top_k in sorted({0, 1, 50, V}):
+                for top_p in (1.0, 0.9, 1e-6):
+                    for temp in (1.0, 0.6):
+                        tag = f"V={V} step={step} k={top_k} p={top_p} t={temp}"
+                        yield launch(f"sample {tag}", B, step, lambda c, o, s, f: ops.sample_select(lg, c, o, s, f, eos, PAD, MIN_NEW, temp, top_k, top_p, SEED))
+                        for wn, (mp, ep, et) in WARPS.items():
+                            kn, km = i32([-7] * B), torch.full((B,), -7.0, device="cuda")
+                            yield launch(f"warped {wn} {tag}", B, step,
+                                         lambda c, o, s, f: ops.sample_select_warped(lg, c, o, s, f, eos, PAD, MIN_NEW, temp, top_k, top_p, SEED, mp, ep, et,
+                                                                                     kept_n=kn, kept_min=km), (kn, km))
+                        for name, (off, tok, dst, node) in trie.items():
+                            nd = node.clone()
+                            yield launch(f"constrained {name} {tag}", B, step,
+                                         lambda c, o, s, f: ops.constrained_select(lg, off, tok, dst, nd, c, o, s, f, eos, PAD, MIN_NEW, temp, top_k, top_p, SEED),
+                                         (nd,))
+    # ---- volume: 8192 rows per launch
+    B, V, eos = 8192, 1025, 2
+    lg = rows(B, V, seed=300)
+    off, tok, dst, node = (i32(a) for a in ([0, V], list(range(V)), [0] * V, [0] * B))
+    kn, km = i32([-7] * B), torch.full((B,), -7.0, device="cuda")
+    yield launch("volume sample", B, 3, lambda c, o, s, f: ops.sample_select(lg, c, o, s, f, eos, PAD, MIN_NEW, 0.6, 50, 0.9, SEED))
+    yield launch("volume warped all", B, 3, lambda c, o, s, f: ops.sample_select_warped(lg, c, o, s, f, eos, PAD, MIN_NEW, 0.6, 50, 0.9, SEED, *WARPS["all"],
+                                                                                        kept_n=kn, kept_min=km), (kn, km))
+    yield launch("volume constrained identity", B, 3,
+                 lambda c, o, s, f: ops.constrained_select(lg, off, tok, dst, node, c, o, s, f, eos, PAD, MIN_NEW, 0.6, 50, 0.9, SEED), (node,))
+
+
+LISTS = {"gemm": _cases, "attn": _attn_cases, "select": _select_cases}
 
 
 def main():

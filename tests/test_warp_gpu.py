@@ -1,4 +1,4 @@
-"""crab_sample_select_warped (csrc/sample_warp.hip) on bare logits.
+"""crab_sample_select_warped (csrc/sample.hip) on bare logits.
 
 (1) all three stages off: cur_ids, out_ids and finished equal crab_sample_select's bit for bit over 8 steps, rows that finish and emit pad
     included.  (2) the stage grid of tests/warp_ref.py - B in {1, 3, 17} x V in {96, 1000, 1025, 32000, 152064}, each stage alone and all three

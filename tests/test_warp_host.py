@@ -1,4 +1,4 @@
-"""min_p / epsilon_cutoff / eta_cutoff without a device: crab_sample_select_warped (csrc/sample_warp.hip) is declared, exported, bound and
+"""min_p / epsilon_cutoff / eta_cutoff without a device: crab_sample_select_warped (csrc/sample.hip) is declared, exported, bound and
 refuses bad arguments before any HIP call; the argument plumbing of the model surface and the engine (off values are the plain sampling
 call, greedy calls ignore the three, the refusals by name); the reference (tests/warp_ref.py) against hand-worked rows and against HF's own
 masks; and the cap on the share of grid rows whose classes leave the kernel a choice - tests/test_warp_gpu.py means something only under it."""
@@ -29,7 +29,7 @@ def test_symbol_is_declared_exported_and_bound_under_abi_13():
     assert _lib.SYMBOLS["crab_sample_select_warped"][1][:18] == _lib.SYMBOLS["crab_sample_select"][1]
     assert lib.crab_abi_version() == 13
     assert callable(ops.sample_select_warped)
-    assert "sample_warp.hip" in os.listdir(os.path.join(ROOT, "crab_amd", "csrc"))
+    assert "sample_select_warped_kernel" in open(os.path.join(ROOT, "crab_amd", "csrc", "sample.hip")).read()       # its kernel has a source
 
 
 def test_entry_point_refuses_bad_arguments_without_a_gpu():

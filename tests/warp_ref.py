@@ -8,7 +8,7 @@ Every token is `KEEP`, `DROP` or `EITHER` as in select_chain_ref.  A new stage i
 moved up and down by the stage's margin: a token is KEEP when the raised threshold still keeps it, DROP when the lowered one still removes
 it.  The parameters are rounded to fp32 first - the kernel's arguments are floats.
 
-The margins - derived from the arithmetic of csrc/sample_warp.hip, never measured from it.  Notation of select_chain_ref's docstring:
+The margins - derived from the arithmetic of csrc/select_core.h, never measured from it.  Notation of select_chain_ref's docstring:
 u = 2^-24, X the largest finite |logit / temperature| of the row, c = ceil(V / 1024); from there
 
     one term       w_i = __expf(x~_i - mx~)              relative error <= (8 X + 3) u        (w of the maximum: __expf(0) = 1 exactly)
