@@ -76,6 +76,26 @@ Attention (csrc/attn.hip, attn_decode_core.h).  o_e = sum_j p_j v_je, p = softma
     This is the one modelled (not worst-case) term of the module; it equals 2 U S_e on rows of a few keys.
     A row without a visible key is zeros: bound 0.
 
+Attention under a peaked softmax (attn_bound_weighted; the laws of tests/attn_laws.py)
+    E above is a maximum over the visible keys.  Under a peaked law it is set by keys of probability about 0 (|s_j - m| = R on a key that weighs
+    e^-R) or by the one key that carries T_j = R, and the slack stops meaning anything.  The same terms, kept per key: key j's contribution
+    to the numerator, p_j v_je, carries the relative error
+        e_j U32,   e_j = (d + 3) T_j + 2 |s_j - m| + 3
+    (its score error (d + 3) U32 T_j passes through exp with derivative 1 in relative terms; the subtraction and log2(e) product, v_exp_f32 and
+    the product with v as above).  The telescoping argument covers the rescale products: whatever chain of running maxima m_1 <= ... <= m a
+    kernel walks between key j's step and the end, the factors multiply to exp(m_1 - m) and their arguments' roundings add up to at most
+    U32 (|s_j - m_1| + |m_1 - m_2| + ... ) <= 2 U32 |s_j - m| - what 2 |s_j - m| pays for, once for the key's own exponential and once for
+    every rescale after it.  So the numerator N_e = sum_j p_j v_je moves by at most U32 sum_j p_j e_j |v_je| and the denominator (1 after
+    normalisation) by U32 sum_j p_j e_j; o_e = N_e / D moves by the first plus |o_e| times the second.  The roundings of the running sums are
+    c(n) U32 on each (numerator relative to S_e, denominator relative to 1), and 1 / l with the last product 2 U32 |o_e|:
+        slack_e = 1.01 U32 [ sum_j p_j e_j |v_je|  +  |o_e| sum_j p_j e_j  +  c(n) (S_e + |o_e|)  +  2 |o_e| ]
+    (1.01 for the second-order terms: every first-order term is below 2^-10.)  With e_j <= E and |o_e| <= S_e each of the four terms is at
+    most its counterpart in (2 E + 2 c(n) + 2) U32 S_e, so slack_e <= 1.01 x the slack of attn_bound (asserted on the old law on the host).
+    The P_e term of the forward kernels and stored() are unchanged; a row without a visible key keeps bound 0.
+    The cap that keeps the slack from hiding a bf16-level defect is max_e slack_e / S_e <= 2^-10 (LAW_SLACK_CAP) under the new laws - at
+    R = 12 it stays under the old 2^-12 as well; R = 90 at d = 128 would pass 2^-10 (e_j = 131 x 93 on the key that holds all the weight), which
+    is why that pair is not among the laws.
+
 RoPE epilogue, fused against unfused beyond 256 rows (dec2_choose may slice K differently)
     Both forms round the projection sum to bf16, rotate with the same pinned fp32 operations (rope_lo / rope_hi) and round again.  The two
     sums lie within the GEMM ceiling c of the exact y: they can round to different bf16 numbers only where y - c and y + c do, by
@@ -91,6 +111,7 @@ U = 2.0 ** -9
 U32 = 2.0 ** -24
 TOL_F32 = 3e-6       # fp32 outputs: accumulation order only (worst 1.15e-6 at K = 6144 on MI355X); tests/test_ops_gpu.py imports it from here
 SLACK_CAP = 2.0 ** -12
+LAW_SLACK_CAP = 2.0 ** -10      # attn_bound_weighted under the laws of tests/attn_laws.py
 HOEFFDING = math.sqrt(2.0 * math.log(2.0 / 1e-12))
 LIP = {"none": 1.0, "relu": 1.0, "gelu": 1.13, "silu": 1.1, "quick_gelu": 1.1, "swiglu_pair": 1.1}
 F64 = torch.float64
@@ -310,6 +331,25 @@ def attn_bound(q, k, v, scale, allow, bias=None, gate=None, kind="decode"):
         f32 = slack + 2 * U * torch.minimum(S, o.abs() + HOEFFDING * n2)
     bound = torch.where(n > 0, stored(o, f32), torch.zeros_like(o))
     return o, bound, float(rel.masked_fill(n == 0, 0.0).max()) if rel.numel() else 0.0
+
+
+def attn_bound_weighted(q, k, v, scale, allow, bias=None, gate=None, kind="decode"):
+    """attn_bound with the per-key terms weighted by the key's probability (module docstring): (o64, bound [B, H, Sq, d], max_e slack_e / S_e)."""
+    o, p, s, T, vv, allow = attn_ref(q, k, v, scale, allow, bias, gate, detail=True)
+    d = q.shape[-1]
+    S = torch.einsum("bhst,bhtd->bhsd", p, vv.abs())
+    n = allow.sum(-1, keepdim=True).to(F64)
+    m = s.masked_fill(~allow, -math.inf).max(-1, keepdim=True).values
+    pe = p * ((d + 3) * T + 2 * (s - m).abs() + 3).masked_fill(~allow, 0.0)            # p_j e_j; 0 on the hidden keys
+    c = 2 * torch.ceil(n / 16) + 32
+    slack = 1.01 * U32 * (torch.einsum("bhst,bhtd->bhsd", pe, vv.abs()) + o.abs() * pe.sum(-1, keepdim=True) + c * (S + o.abs()) + 2 * o.abs())
+    f32 = slack
+    if kind == "fwd":
+        n2 = torch.einsum("bhst,bhtd->bhsd", p * p, vv * vv).sqrt()
+        f32 = slack + 2 * U * torch.minimum(S, o.abs() + HOEFFDING * n2)
+    bound = torch.where(n > 0, stored(o, f32), torch.zeros_like(o))
+    rel = torch.where((n > 0) & (S > 0), slack / S.clamp_min(1e-300), torch.zeros_like(S))
+    return o, bound, float(rel.max()) if rel.numel() else 0.0
 
 
 # ------------------------------------------------------------------------------------------------------------------- RoPE epilogue pair

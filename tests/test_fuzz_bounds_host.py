@@ -328,6 +328,9 @@ def test_fuzzers_hold_no_tolerance_literal():
     assert set(LITERAL.findall(_src("fuzz_gemm.py"))) <= {"1e-5"}           # the post-norm's eps, an operand
     assert not LITERAL.findall(_src("fuzz_attn.py"))
     assert not LITERAL.findall(_src("fuzz_rope_epilogue.py"))
+    with open(os.path.join(ROOT, "tests", "test_attn_laws_gpu.py")) as f:
+        laws_src = f.read()
+    assert not LITERAL.findall(laws_src) and "attn_bound_weighted" in laws_src and "torch.softmax" not in laws_src
     ops_src = _src("fuzz_ops.py")
     norm = ops_src[ops_src.index('if kind in ("rmsnorm", "layernorm")'):ops_src.index('elif kind == "embedding"')]
     assert set(LITERAL.findall(norm)) <= {"1e-5", "1e-6", "1e-12"}          # the eps choices
