@@ -219,6 +219,8 @@ SYMBOLS = {
     "crab_beam_merge": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
                              _vp, _vp]),
     "crab_kv_beam_reorder": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "crab_kv_compact_rows": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "crab_sample_select_rows": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _i64, _vp, _vp, _i, _i, _i, _f, _i, _f, C.c_uint64, _f, _f, _f, _vp]),
     "crab_cfg_mix": (_i, [_vp, _vp, _vp, _i64, _i, _i, _f, _vp, _vp, _i64]),
     "crab_cfg_follow": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _vp, _i]),
     "crab_attn_verify": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _vp, _f, _vp]),

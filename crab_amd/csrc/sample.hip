@@ -16,6 +16,9 @@
 // Both kernels are instantiations of select_draw (select_core.h, where the stages are described): with all three stages off the warped kernel
 // runs the plain kernel's operations in its order and the ids are equal bit for bit (tests/test_warp_gpu.py).  A row without a finite token
 // (mx = -inf, every weight NaN) passes nothing anywhere and both kernels emit token 0.
+// sample_select_rows_kernel<WARP> (crab_sample_select_rows) is either of the two with one more operand, row_ids: block r works on row r of every
+// buffer and hands row_ids[r] to select_draw as the row of the draw's key - the rows of a wave that shed its finished rows (csrc/kv_compact.hip)
+// keep the random streams they had.  Same select_draw, same token_epilogue: bit-identical to the kernel above of either form on the same logits.
 // Cost of the stages: 1 (min_p) + 2 (epsilon) + 2 (eta) passes over the row next to the 67 of the two bisections, + 1 when kept_n / kept_min
 // are wanted.
 #include "common.h"
@@ -65,7 +68,48 @@ __global__ __launch_bounds__(1024) void sample_select_warped_kernel(const float*
     if (threadIdx.x == 0) token_epilogue(pick, b, step, cur_ids, out_ids, ld_out, finished, eos_id, pad_id);
 }
 
+// The rows of a compacted wave (csrc/kv_compact.hip): block r works on row r of every buffer, but its draw is keyed by row_ids[r], the index the
+// row had before the wave shed its finished rows - the random stream of a row does not depend on which rows left.  WARP as select_draw's.
+template <bool WARP>
+__global__ __launch_bounds__(1024) void sample_select_rows_kernel(const float* __restrict__ logits, long ldl, int V, int64_t* __restrict__ cur_ids,
+                                                                  int64_t* __restrict__ out_ids, long ld_out, const int* __restrict__ step_dev,
+                                                                  int* __restrict__ finished, int eos_id, int pad_id, int min_new, float inv_t,
+                                                                  int top_k, float top_p, unsigned long long seed, float min_p, float eps_cut,
+                                                                  float eta_cut, const int* __restrict__ row_ids) {
+    __shared__ SelectShared sh;
+    const int r = blockIdx.x, step = step_dev[0];
+    const TokenItems items{logits + (long)r * ldl, inv_t, (eos_id >= 0 && step < min_new) ? eos_id : -1};
+    int pick;
+    if constexpr (WARP) pick = select_draw<true>(sh, items, V, row_ids[r], step, top_k, top_p, seed, SelectWarp{min_p, eps_cut, eta_cut, nullptr, nullptr});
+    else pick = select_draw<false>(sh, items, V, row_ids[r], step, top_k, top_p, seed);
+    if (threadIdx.x == 0) token_epilogue(pick, r, step, cur_ids, out_ids, ld_out, finished, eos_id, pad_id);
+}
+
 }  // namespace
+
+extern "C" int crab_sample_select_rows(crab_ctx* ctx, void* stream, const float* logits, int64_t ldl, int B, int V, int64_t* cur_ids,
+                                       int64_t* out_ids, int64_t ld_out, const int32_t* step_dev, int32_t* finished, int eos_id, int pad_id,
+                                       int min_new_tokens, float temperature, int top_k, float top_p, uint64_t seed, float min_p,
+                                       float epsilon_cutoff, float eta_cutoff, const int32_t* row_ids) {
+    if (!ctx) return CRAB_E_INVALID;
+    if (!logits || !cur_ids || !out_ids || !step_dev || !finished || !row_ids || B <= 0 || V <= 0)
+        return crab_fail(ctx, CRAB_E_INVALID, "sample_select_rows: bad argument");
+    if (!(temperature > 0.f) || !(top_p > 0.f) || top_p > 1.0f || top_k < 0) return crab_fail(ctx, CRAB_E_INVALID, "sample_select_rows: temperature > 0, 0 < top_p <= 1, top_k >= 0");
+    if (!(min_p >= 0.f && min_p <= 1.0f)) return crab_fail(ctx, CRAB_E_INVALID, "sample_select_rows: 0 <= min_p <= 1 (0 = off)");
+    if (!(epsilon_cutoff >= 0.f && epsilon_cutoff < 1.0f)) return crab_fail(ctx, CRAB_E_INVALID, "sample_select_rows: 0 <= epsilon_cutoff < 1 (0 = off)");
+    if (!(eta_cutoff >= 0.f && eta_cutoff < 1.0f)) return crab_fail(ctx, CRAB_E_INVALID, "sample_select_rows: 0 <= eta_cutoff < 1 (0 = off)");
+    // all three stages off: the plain kernel's operations in its order (select_draw<false>), else the warped ones - bit-identical to
+    // crab_sample_select / crab_sample_select_warped on the same logits either way
+    if (min_p == 0.f && epsilon_cutoff == 0.f && eta_cutoff == 0.f)
+        hipLaunchKernelGGL(sample_select_rows_kernel<false>, dim3(B), dim3(1024), 0, (hipStream_t)stream, logits, (long)ldl, V, cur_ids, out_ids,
+                           (long)ld_out, step_dev, finished, eos_id, pad_id, min_new_tokens, 1.0f / temperature, top_k, top_p,
+                           (unsigned long long)seed, 0.f, 0.f, 0.f, row_ids);
+    else
+        hipLaunchKernelGGL(sample_select_rows_kernel<true>, dim3(B), dim3(1024), 0, (hipStream_t)stream, logits, (long)ldl, V, cur_ids, out_ids,
+                           (long)ld_out, step_dev, finished, eos_id, pad_id, min_new_tokens, 1.0f / temperature, top_k, top_p,
+                           (unsigned long long)seed, min_p, epsilon_cutoff, eta_cutoff, row_ids);
+    return crab_check_launch(ctx, "sample_select_rows");
+}
 
 extern "C" int crab_sample_select(crab_ctx* ctx, void* stream, const float* logits, int64_t ldl, int B, int V, int64_t* cur_ids, int64_t* out_ids,
                                   int64_t ld_out, const int32_t* step_dev, int32_t* finished, int eos_id, int pad_id, int min_new_tokens,

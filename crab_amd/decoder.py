@@ -36,6 +36,7 @@ RAGGED_PAD_MAX = 0.06     # a coalesced wave whose batches differ in length is p
 WEIGHT_DTYPES = ("bf16", "fp8_e4m3")       # GenerationEngine(weight_dtype=...): bf16 decoder weights | opt-in FP8 (e4m3fn codes + fp32 row scales) for decode steps of <= 16 rows
 W8_MAX_ROWS = 16                            # rows up to which a decode step streams the FP8 weights (the regime of gemm_skinny_dma_w8_kernel, csrc/skinny.hip)
 KV_CACHE_DTYPES = ("bf16", "fp8_e4m3")     # GenerationEngine(kv_cache_dtype=...): the default bf16 cache | the opt-in FP8 (OCP e4m3fn) cache with fp32 row scales
+SHED_MIN_STEPS_LEFT = 4   # shed_finished: a look sheds only while at least this many decode steps remain (the measured break-even is ~3 steps)
 EOS_CHECK_EVERY = 16      # decode steps between two host reads of the `finished` flags: the only synchronisation inside the step loop (_run_steps)
 NATIVE_LAYERS = True      # False: issue every launch of a layer from Python (A/B runs and the sequencer-equivalence tests)
 
@@ -262,6 +263,81 @@ def normalize_sampling(sampling, constrained: bool = False):
 def reseed_sampling(sampling, offset: int):
     """The sampling tuple (of either length) of a later wave or group of one call: its seed moved by `offset`, everything else kept."""
     return None if sampling is None else tuple(sampling[:3]) + (sampling[3] + offset,) + tuple(sampling[4:])
+
+
+def shed_default_ladder():
+    """The row counts a shedding wave (shed_finished=True) steps down through: the powers of two from 4 to ops.DECODE_MAX_ROWS.  They contain the
+    counts at which the decode step changes kernels - 16 (the M <= 16 projections), 64 (CRAB_DEC_MIN_ROWS), 256 and ops.DECODE_MAX_ROWS - and
+    every rung is half of the next: a wave that has lost half of its rows always finds a rung, and the rows a call moves over all of its
+    sheds are bounded by a geometric series (< 2 x the rows of its first shed).  Below 4 rows a step is a latency chain that no row count
+    shortens.  A decision, not a measured optimum."""
+    top = int(ops.DECODE_MAX_ROWS)
+    return tuple(sorted({r for r in (4, 8, 16, 32, 64, 128, 256) if r < top} | {top}))
+
+
+def shed_ladder(shed_finished):
+    """The `shed_finished` argument as a ladder: None / False -> None (the option is off: the call is the call without the argument), True ->
+    shed_default_ladder(), a tuple / list of row counts -> that tuple, which has to be strictly increasing and positive (ValueError by name)."""
+    if shed_finished is None or shed_finished is False:
+        return None
+    if shed_finished is True:
+        return shed_default_ladder()
+    if not isinstance(shed_finished, (tuple, list)) or not shed_finished or any(isinstance(r, bool) or not isinstance(r, int) for r in shed_finished):
+        raise ValueError(f"`shed_finished` has to be None, a bool or a sorted tuple of row counts, but is {shed_finished!r}")
+    lad = tuple(int(r) for r in shed_finished)
+    if any(r < 1 for r in lad):
+        raise ValueError(f"`shed_finished` = {lad}: every rung has to be a positive row count")
+    if any(b <= a for a, b in zip(lad, lad[1:])):
+        raise ValueError(f"`shed_finished` = {lad}: the rungs have to be sorted (strictly increasing)")
+    return lad
+
+
+def shed_rung(ladder, n_live: int, B_cur: int) -> Optional[int]:
+    """The row count a state of B_cur rows with n_live unfinished ones sheds to: the smallest rung >= n_live when that is below B_cur, else None
+    (no rung holds the live rows, or the state already is that small: nothing happens)."""
+    for r in ladder:
+        if r >= n_live:
+            return r if r < B_cur else None
+    return None
+
+
+def check_shed(shed_finished, shed_every=None, constraint=None, processors=None, return_logprobs: bool = False, return_hidden: bool = False,
+               decode_streams: int = 1, kv_cache_dtype: str = "bf16", return_step_logits: bool = False, coalesced: bool = False):
+    """shed_ladder + what a shedding call refuses BY NAME, before any device work (the style of check_lookup).  A shed gathers the per-row words a plain greedy / sampling step owns and moves bf16 cache rows; every option below
+    owns further per-row device state that would have to move with them.  Returns (ladder, steps between looks) or None when the option is off."""
+    s_name, e_name, c_name, p_name, lp_name, h_name, d_name, sl_name = ("shed_finished", "shed_every", "constraint", "processors", "return_logprobs",
+                                                                         "return_hidden", "decode_streams", "return_step_logits")
+    lad = shed_ladder(shed_finished)
+    if lad is None:
+        return None
+    every = EOS_CHECK_EVERY if shed_every is None else int(shed_every)
+    if every < 1:
+        raise ValueError(f"`{e_name}` has to be a strictly positive number of steps, but is {shed_every}")
+    if constraint is not None:
+        raise NotImplementedError(f"{s_name} with {c_name}: the trie node of every row (crab_constrained_select) would have to follow its row")
+    if normalize_processors(processors) is not None:
+        raise NotImplementedError(f"{s_name} with {p_name}: the save area of crab_logits_edit / crab_logits_restore is laid out per row of the wave")
+    if return_logprobs:
+        raise NotImplementedError(f"{s_name} with {lp_name}: the log-probability planes are laid out per row of the wave")
+    if return_hidden:
+        raise NotImplementedError(f"{s_name} with {h_name}: the hidden rows are kept per row of the wave")
+    if int(decode_streams) > 1:
+        raise NotImplementedError(f"{s_name} with {d_name} = {decode_streams}: the groups of a split wave step in lockstep on their own streams")
+    if kv_cache_dtype == "fp8_e4m3":
+        raise NotImplementedError(f'{s_name} with kv_cache_dtype="fp8_e4m3": crab_kv_compact_rows moves the bf16 cache (the fp8 row scales would have to move too)')
+    if coalesced and return_step_logits:
+        raise NotImplementedError(f"{s_name} with {sl_name} in the coalesced form: the per-step logits of a shedding wave are kept by generate() only")
+    return lad, every
+
+
+class _Shed:
+    """One shedding call: the ladder, the steps between looks, and what the call records - log: (step, rows_before, rows_after, rows_moved) per
+    shed; captures: HIP graphs captured by this call.  out: the result buffer of the wave in progress (_run_steps)."""
+
+    def __init__(self, ladder, every: int):
+        self.ladder, self.every = tuple(ladder), int(every)
+        self.log, self.captures = [], 0
+        self.out = None
 
 
 def _pack_waves(Bs: List[int], cap: int) -> List[List[int]]:
@@ -787,7 +863,10 @@ class GenerationEngine:
         native_ok = key_mask is None and (not masked or (vt is not None and pos_dev is None and
                                                          (pos_ids is None or (pos_ids.dtype == torch.int32 and pos_ids.stride(1) == 1))))
         last_rows = bool(last_rows) and vt is not None and S > 1 and key_mask is None and pos_dev is None
-        if prefix is None and not verify and NATIVE_LAYERS and not timed and native_ok and contig and (vt is not None or S == 1):
+        # the sequencer takes the layer stride on its own (io.cache_layer_stride): the first rows of every layer of a larger allocation - the
+        # cache of a wave that shed rows (_shed_to) - are a cache to it as long as the rows of a layer are packed
+        packed = contig or (kc.dim() == 5 and kc.stride() == vc.stride() and kc[0].is_contiguous() and vc[0].is_contiguous())
+        if prefix is None and not verify and NATIVE_LAYERS and not timed and native_ok and packed and (vt is not None or S == 1):
             self._layers_native(ws, B, S, kc, vc, b0, Tmax, pos0, pos_dev, vt, t0, row_off, pos_ids, kv_start, last_rows, kv_scales, w8)
             return x, h
         u_qkv = None                                   # router output for the q|k|v group when a producer epilogue made it
@@ -1195,6 +1274,12 @@ class GenerationEngine:
                                    st.finished, st.eos, st.pad, st.min_new, t, k, p_, seed + 7919 * st.slot)
         elif st.sampling is None:
             ops.greedy_select(logits, st.cur_ids, st.out_ids, st.step_dev, st.finished, st.eos, st.pad, st.min_new)
+        elif getattr(st, "rows", None) is not None:
+            # the child state of a wave that shed rows (_shed_to): every row draws under the index it had in the whole wave, so the random
+            # stream is the unshed call's; one entry for both tuple forms (it picks the plain or the warped pipeline itself)
+            t, k, p_, seed = st.sampling[:4]
+            ops.sample_select_rows(st.rows, logits, st.cur_ids, st.out_ids, st.step_dev, st.finished, st.eos, st.pad, st.min_new, t, k, p_,
+                                   seed + 7919 * st.slot, *st.sampling[4:])
         elif len(st.sampling) == 4:
             t, k, p_, seed = st.sampling
             ops.sample_select(logits, st.cur_ids, st.out_ids, st.step_dev, st.finished, st.eos, st.pad, st.min_new, t, k, p_, seed + 7919 * st.slot)
@@ -1301,6 +1386,9 @@ class GenerationEngine:
             st.stop_dev = torch.tensor(stops, dtype=torch.int32).to(dev) if stops else None
             st.cfg = (float(cfg[0]), int(cfg[1])) if cfg is not None else None
             st.guided = torch.empty((int(cfg[1]), V), device=dev, dtype=torch.float32) if cfg is not None else None
+            # shed_finished: the child states of this state, (rows, weight form) -> _DecodeState (_shed_to).  They live and die with their
+            # parent - its key stands for everything theirs bake in - so invalidate() and a changed key drop them with it
+            st.rows, st.children = None, {}
             self._dec[slot] = st
         st.S = S
         st.cur_ids.zero_(); st.out_ids.fill_(pad_token_id if pad_token_id is not None else 0); st.finished.zero_()
@@ -1445,8 +1533,18 @@ class GenerationEngine:
                  pad_token_id: Optional[int] = None, min_new_tokens: int = 0, prefill_chunk: int = 0, use_graph: bool = True,
                  return_step_logits: bool = False, return_hidden: bool = False, decode_streams: int = 1,
                  return_first_logits: bool = False, sampling=None, kv_cache_dtype: Optional[str] = None, weight_dtype: Optional[str] = None,
-                 constraint=None, return_logprobs: bool = False, processors=None):
+                 constraint=None, return_logprobs: bool = False, processors=None, shed_finished=None, shed_every: Optional[int] = None):
         """kv_cache_dtype / weight_dtype: "bf16" / "fp8_e4m3" for this call (None: the engine's); see _generate for the rest.
+        shed_finished (opt-in; None / False: off, the call is the call without the argument): a wave stops carrying the rows that have
+        emitted EOS.  True: the default ladder (shed_default_ladder), a sorted tuple of row counts: that ladder.  Every shed_every steps
+        (default EOS_CHECK_EVERY) the EOS check reads the `finished` vector; when the unfinished rows fit a smaller rung B', their cache rows
+        move to the front in place (crab_kv_compact_rows) and a child state of B' rows steps on (_shed_to) - the attention stops reading the
+        finished rows' keys and the projections run at B' rows.  The result is the unshed call's: same shape, trimming and padding; the
+        surviving rows run the kernels B' selects, so ids / logits agree within the decoder's bf16 bound, not bit for bit (the rule of
+        coalesce and decode_streams); sample mode keeps every row's random stream (crab_sample_select_rows).  return_step_logits holds zeros
+        where a row had been shed.  last_plan["shed"] = [(step, rows_before, rows_after, rows_moved)], last_plan["shed_captures"] = graphs
+        captured by the call.  Refused by name (check_shed): constraint, processors, return_logprobs, return_hidden, decode_streams > 1,
+        kv_cache_dtype="fp8_e4m3".
         processors = (repetition_penalty, no_repeat_ngram_size, stop_token_ids) or None: HF's RepetitionPenaltyLogitsProcessor and
         NoRepeatNGramLogitsProcessor over the GENERATED tokens (generate() with inputs_embeds starts HF from an empty input_ids, so the prompt
         never enters them) and stop ids BEYOND eos_token_id (HF's list-valued eos_token_id: any of them finishes a row, min_new_tokens
@@ -1467,13 +1565,33 @@ class GenerationEngine:
         (HF's warped `scores` are not reproduced).  Written inside the decode step (csrc/logprob.hip): no host sync, nothing of size B x V kept."""
         sampling = normalize_sampling(sampling, constraint is not None)
         proc = check_processors(processors, min_new_tokens, constraint is not None, return_logprobs, eos_token_id)      # refused before any device work
+        plan = check_shed(shed_finished, shed_every, constraint, proc, return_logprobs, return_hidden, decode_streams,
+                          self._kv_mode if kv_cache_dtype is None else self.check_kv_cache_dtype(kv_cache_dtype))
         cons, = self._constraints(constraint, [int(embeds.shape[0])], eos_token_id, min_new_tokens, flat=True)
+        if plan is not None:
+            return self._call_shedding(plan, kv_cache_dtype, weight_dtype, self._generate, embeds, max_new_tokens, eos_token_id, pad_token_id,
+                                       min_new_tokens, prefill_chunk, use_graph, return_step_logits, return_hidden, decode_streams,
+                                       return_first_logits, sampling, cons, return_logprobs, processors=proc)
         return self._call(kv_cache_dtype, weight_dtype, self._generate, embeds, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens,
                           prefill_chunk, use_graph, return_step_logits, return_hidden, decode_streams, return_first_logits, sampling, cons,
                           return_logprobs, processors=proc)
 
+    def _call_shedding(self, plan, kv_cache_dtype, weight_dtype, fn, *a, **k):
+        """_call for a shedding call (plan = check_shed's (ladder, steps between looks)): fn gets the call's _Shed, and last_plan is stamped with
+        what it recorded.  A retry after an eviction (_retry_after_eviction) starts the record again."""
+        shed = _Shed(*plan)
+
+        def run(*a_, **k_):
+            shed.log, shed.captures = [], 0
+            return fn(*a_, shed=shed, **k_)
+
+        res = self._call(kv_cache_dtype, weight_dtype, run, *a, **k)
+        if isinstance(self.last_plan, dict):
+            self.last_plan["shed"], self.last_plan["shed_captures"] = list(shed.log), shed.captures
+        return res
+
     def _run_steps(self, sts: List["_DecodeState"], max_new_tokens: int, graphed: bool, side_streams: bool, retire: bool, on_step=None,
-                   sampled_step=None):
+                   sampled_step=None, shed: Optional["_Shed"] = None):
         """The decode steps 1 .. max_new_tokens - 1 of started states (step 0, the first token, is _start's): THE step loop of the engine.
         graphed: every state's step is captured under its own scratch slot (or its graph reused, _capture) and replayed; else the step runs
         eagerly.  side_streams: every state steps on a HIP stream of its own, forked from the current stream before the first step and joined
@@ -1483,11 +1601,19 @@ class GenerationEngine:
           retire = False: every state keeps stepping until ALL of them have finished (generate(decode_streams > 1): the groups are one call,
                           their buffers are joined column by column).
         on_step(sts[0]) runs after every step.  sampled_step(step, sts[0]) is asked before every graphed step of the FIRST state and returns
-        True when it has run that step itself (bench.py's roofline sampling); the state is device-resident, so replays continue after it."""
+        True when it has run that step itself (bench.py's roofline sampling); the state is device-resident, so replays continue after it.
+        shed (shed_finished; ONE state on the current stream): the EOS check reads the `finished` vector instead of its .all() - still the
+        loop's only synchronisation, every shed.every steps - and when the unfinished rows fit a smaller rung of the ladder, sts[0] is
+        replaced IN THE LIST by the child state that carries them on (_shed_to).  The ids of the whole wave are then in shed.out."""
         main = torch.cuda.current_stream()
         graphs, streams = [], []
+        if shed is not None:
+            assert len(sts) == 1 and not side_streams and sts[0].lookup is None, "a shedding wave is one state on the current stream"
+            shed.out, root = None, sts[0]
         for st in sts:
             with _ws_slot(st.slot):
+                if shed is not None and graphed and st.graph is None:
+                    shed.captures += 1
                 graphs.append(self._capture(st) if graphed else None)
             streams.append(torch.cuda.Stream() if side_streams else main)
         if side_streams:
@@ -1496,7 +1622,7 @@ class GenerationEngine:
         eos_on = any(e >= 0 for e in sts[0].eos_all) or sts[0].lookup is not None      # a lookup state finishes early by max_new_tokens as well
         # a verify step of a lookup state emits up to k + 1 tokens, so the call can end at ANY step, and every step past its end is a whole
         # (k + 1)-row pass over the weights that changes nothing: such a state is read after every step (one 4-byte read against a >= 4 ms step)
-        check_every = 1 if sts[0].lookup is not None else EOS_CHECK_EVERY
+        check_every = 1 if sts[0].lookup is not None else (shed.every if shed is not None else EOS_CHECK_EVERY)
         live = list(range(len(sts)))
         for step in range(1, max_new_tokens):
             for g in live:
@@ -1508,7 +1634,22 @@ class GenerationEngine:
                         graphs[g].replay()
             if on_step is not None:
                 on_step(sts[0])
-            if eos_on and step % check_every == 0:
+            if eos_on and step % check_every == 0 and shed is not None:
+                fin = sts[0].finished.tolist()                 # the one read of this look (the fillers of a rung are finished by construction)
+                rows_live = [i for i, f in enumerate(fin) if not f]
+                if not rows_live:
+                    break
+                Bp = shed_rung(shed.ladder, len(rows_live), sts[0].B)
+                # a shed costs about three steps of what it saves per step: near the end of the call it is pure loss
+                if Bp is not None and max_new_tokens - 1 - step >= SHED_MIN_STEPS_LEFT:
+                    if shed.out is None:
+                        shed.out = torch.empty_like(root.out_ids)
+                    sts[0] = self._shed_to(root, sts[0], rows_live, Bp, shed, step)
+                    with _ws_slot(sts[0].slot):
+                        if graphed and sts[0].graph is None:
+                            shed.captures += 1
+                        graphs[0] = self._capture(sts[0]) if graphed else None
+            elif eos_on and step % check_every == 0:
                 still = []
                 for g in live:
                     if still and not retire:
@@ -1520,6 +1661,8 @@ class GenerationEngine:
                     break
                 if retire:
                     live = still
+        if shed is not None and sts[0].rows is not None:
+            self._shed_flush(sts[0], shed, 0)                  # the rows that stepped to the end
         if side_streams:
             for sg in streams:
                 main.wait_stream(sg)
@@ -1527,7 +1670,8 @@ class GenerationEngine:
     def _generate(self, embeds: torch.Tensor, max_new_tokens: int, eos_token_id: Optional[int] = None,
                   pad_token_id: Optional[int] = None, min_new_tokens: int = 0, prefill_chunk: int = 0, use_graph: bool = True,
                   return_step_logits: bool = False, return_hidden: bool = False, decode_streams: int = 1,
-                  return_first_logits: bool = False, sampling=None, constraint=None, return_logprobs: bool = False, processors=None):
+                  return_first_logits: bool = False, sampling=None, constraint=None, return_logprobs: bool = False, processors=None,
+                  shed: Optional["_Shed"] = None):
         """Greedy generation from inputs_embeds only, as UnifiedForCausalLM.generate drives HF generate
         (unified_llama.py:262-267): positions 0..S-1 (left pads attended), returns ONLY new ids.
 
@@ -1547,7 +1691,7 @@ class GenerationEngine:
         if len(groups) > 1:
             return self._generate_split(groups, embeds, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, prefill_chunk, use_graph,
                                         return_step_logits, return_hidden, return_first_logits, sampling, constraint, return_logprobs,
-                                        processors=processors)
+                                        processors=processors, shed=shed)
         graphed = use_graph and max_new_tokens > 2
         G = decode_streams if (decode_streams > 1 and graphed and B >= decode_streams and
                                not return_step_logits and not return_hidden) else 1
@@ -1556,7 +1700,12 @@ class GenerationEngine:
         def sink(st):
             if return_first_logits and len(first_logits) < G:
                 first_logits.append(st.logits.clone())
-            if return_step_logits:
+            if return_step_logits and st.rows is not None:
+                # a child state of a wave that shed rows: its real rows under their indices in the whole wave, zeros where a row has left
+                full = torch.zeros((B,) + tuple(st.logits.shape[1:]), device=st.logits.device, dtype=st.logits.dtype)
+                full[st.rows_idx] = st.logits[:st.n_real]
+                step_logits.append(full)
+            elif return_step_logits:
                 step_logits.append(st.logits.clone())
             if return_hidden:
                 hiddens.append(st.hn.clone())
@@ -1582,11 +1731,14 @@ class GenerationEngine:
         if ops.PROFILER is not None:
             ops.PROFILER.mark("prefill_end")
         # the groups are ONE call: all of them step until all have finished (a retired group's buffer would hold the fill value, not its pad id)
-        self._run_steps(sts, max_new_tokens, graphed, G > 1, False, sink, sampled_step)
+        self._run_steps(sts, max_new_tokens, graphed, G > 1, False, sink, sampled_step, shed=shed)
         if ops.PROFILER is not None:
             ops.PROFILER.mark("decode_end")
         n_done = int(sts[0].step_dev.item())
-        out = _trim_at_eos(sts[0].out_ids if G == 1 else torch.cat([st.out_ids for st in sts], 0), n_done, sts[0].eos_all)
+        if shed is not None and shed.out is not None:         # the wave shed rows: its ids were assembled under the rows' original indices
+            out = _trim_at_eos(shed.out, n_done, sts[0].eos_all)
+        else:
+            out = _trim_at_eos(sts[0].out_ids if G == 1 else torch.cat([st.out_ids for st in sts], 0), n_done, sts[0].eos_all)
         # st.out_ids is the persistent, graph-baked buffer the next generate() refills: hand the caller its own tensor (HF
         # generate returns fresh tensors; a caller that collects results over batches must not see them overwritten)
         res = [out.clone()]
@@ -1605,8 +1757,11 @@ class GenerationEngine:
                       pad_token_id: Optional[int] = None, min_new_tokens: int = 0, use_graph: bool = True, sampling=None,
                       return_first_logits: bool = False, coalesce: bool = False, max_rows: Optional[int] = None,
                       return_step_logits: bool = False, return_hidden: bool = False, kv_cache_dtype: Optional[str] = None,
-                      weight_dtype: Optional[str] = None, constraint=None, return_logprobs: bool = False, processors=None):
+                      weight_dtype: Optional[str] = None, constraint=None, return_logprobs: bool = False, processors=None, shed_finished=None,
+                      shed_every: Optional[int] = None):
         """kv_cache_dtype / weight_dtype: "bf16" / "fp8_e4m3" for this call (None: the engine's); see _generate_many for the rest.
+        shed_finished / shed_every (coalesce=True only): as in generate(), for every ragged wave of the call - a batch's result is still what
+        its rows produced, trimmed per batch from the assembled buffer.  Refused by name as in generate(), and with return_step_logits.
         processors = (repetition_penalty, no_repeat_ngram_size, stop_token_ids) or None, as in generate(): every row's own generated tokens
         are its history, wherever the row decodes (in-flight states, ragged waves).
         return_logprobs: every batch's result gains a LAST element, fp32 [B_g, n_g, 2], as in generate(); a row's scores follow the row into the
@@ -1615,7 +1770,16 @@ class GenerationEngine:
         their rows into the in-flight states and the ragged waves."""
         sampling = normalize_sampling(sampling, constraint is not None)
         proc = check_processors(processors, min_new_tokens, constraint is not None, return_logprobs, eos_token_id)
+        plan = check_shed(shed_finished, shed_every, constraint, proc, return_logprobs, return_hidden, 1,
+                          self._kv_mode if kv_cache_dtype is None else self.check_kv_cache_dtype(kv_cache_dtype), return_step_logits, coalesced=True)
+        if plan is not None and not coalesce:
+            raise NotImplementedError("shed_finished with coalesce=False: the batches in flight are states of their own that retire as a whole "
+                                      "(use coalesce=True, or generate() per batch)")
         cons = self._constraints(constraint, [int(e.shape[0]) for e in embeds_list], eos_token_id, min_new_tokens) if constraint is not None else None
+        if plan is not None:
+            return self._call_shedding(plan, kv_cache_dtype, weight_dtype, self._generate_many, embeds_list, max_new_tokens, eos_token_id,
+                                       pad_token_id, min_new_tokens, use_graph, sampling, return_first_logits, coalesce, max_rows,
+                                       return_step_logits, return_hidden, cons, return_logprobs, processors=proc)
         return self._call(kv_cache_dtype, weight_dtype, self._generate_many, embeds_list, max_new_tokens, eos_token_id, pad_token_id,
                           min_new_tokens, use_graph, sampling, return_first_logits, coalesce, max_rows, return_step_logits, return_hidden, cons,
                           return_logprobs, processors=proc)
@@ -1624,7 +1788,7 @@ class GenerationEngine:
                        pad_token_id: Optional[int] = None, min_new_tokens: int = 0, use_graph: bool = True, sampling=None,
                        return_first_logits: bool = False, coalesce: bool = False, max_rows: Optional[int] = None,
                        return_step_logits: bool = False, return_hidden: bool = False, constraints=None, return_logprobs: bool = False,
-                       processors=None):
+                       processors=None, shed=None):
         """Several INDEPENDENT batches in flight: each element of `embeds_list` ([B_i, S_i, D], its own prompt length and left padding, i.e.
         exactly what one generate() call of the reference's eval loop gets) becomes one decode group with its own KV cache, decode state
         and captured HIP graph; the groups are prefilled one after the other and their decode steps are replayed on separate HIP streams.
@@ -1654,11 +1818,11 @@ class GenerationEngine:
         if coalesce and (G > 1 or return_step_logits or return_hidden):
             return self._generate_coalesced(embeds_list, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling,
                                             return_first_logits, max_rows, return_step_logits, return_hidden, cons, return_logprobs,
-                                            processors=processors)
+                                            processors=processors, shed=shed)
         if G == 1:
             return [self._generate(embeds_list[0], max_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id, min_new_tokens=min_new_tokens,
                                    use_graph=use_graph, sampling=sampling, return_first_logits=return_first_logits, constraint=cons[0],
-                                   return_logprobs=return_logprobs, processors=processors)]
+                                   return_logprobs=return_logprobs, processors=processors, shed=shed)]
         need = sum(e.shape[0] * self.bytes_per_sequence(e.shape[1], max_new_tokens) for e in embeds_list) + self.fixed_bytes(max(e.shape[0] for e in embeds_list),
                                                                                                                             max(e.shape[1] for e in embeds_list))
         budget = self.memory_budget(0, 0, slots=G)
@@ -1688,7 +1852,7 @@ class GenerationEngine:
 
     def _generate_coalesced(self, embeds_list, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling,
                             return_first_logits, max_rows, return_step_logits=False, return_hidden=False, cons=None, return_logprobs=False,
-                            processors=None):
+                            processors=None, shed=None):
         """generate_many(coalesce=True): pack the batches, in order, into waves of at most `cap` rows (the weight-streaming regime of the decode
         projections, and what the device's memory holds at the longest prompt), run every wave as one ragged batch."""
         Bs = [int(e.shape[0]) for e in embeds_list]
@@ -1707,19 +1871,19 @@ class GenerationEngine:
                 outs[g] = self._generate(embeds_list[g], max_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
                                          min_new_tokens=min_new_tokens, use_graph=use_graph, sampling=sampling, return_first_logits=return_first_logits,
                                          return_step_logits=return_step_logits, return_hidden=return_hidden, constraint=cons[g],
-                                         return_logprobs=return_logprobs, processors=processors)
+                                         return_logprobs=return_logprobs, processors=processors, shed=shed)
                 continue
             # the rows of the wave are the rows of its batches in wave order: so are their trie roots
             wc = _Constraint(cons[w[0]].dev, [r for g in w for r in cons[g].roots]) if cons[w[0]] is not None else None
             res = self._ragged_wave([embeds_list[g] for g in w], max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling,
-                                    return_first_logits, return_step_logits, return_hidden, wc, return_logprobs, processors=processors)
+                                    return_first_logits, return_step_logits, return_hidden, wc, return_logprobs, processors=processors, shed=shed)
             for g, r in zip(w, res):
                 outs[g] = r
         self.last_plan = plan
         return outs
 
     def _ragged_wave(self, embeds_list, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling, return_first_logits,
-                     return_step_logits=False, return_hidden=False, constraint=None, return_logprobs=False, processors=None):
+                     return_step_logits=False, return_hidden=False, constraint=None, return_logprobs=False, processors=None, shed=None):
         firsts, steps = [], []
 
         def sink(st):
@@ -1735,17 +1899,19 @@ class GenerationEngine:
                                     return_logprobs, processors=processors)
         if ops.PROFILER is not None:
             ops.PROFILER.mark("prefill_end")
-        self._run_steps([st], max_new_tokens, use_graph and max_new_tokens > 2, False, True,
-                        sink if (return_step_logits or return_hidden) else None)
+        sts = [st]
+        self._run_steps(sts, max_new_tokens, use_graph and max_new_tokens > 2, False, True,
+                        sink if (return_step_logits or return_hidden) else None, shed=shed)
         if ops.PROFILER is not None:
             ops.PROFILER.mark("decode_end")
-        n_done = int(st.step_dev.item())
+        n_done = int(sts[0].step_dev.item())                   # a wave that shed rows ends in a child state: the counters went with it
+        ids = shed.out if (shed is not None and shed.out is not None) else st.out_ids      # ... and its ids were assembled in shed.out
         sl = torch.stack(steps, 1) if (return_step_logits or return_hidden) else None
         outs, r0 = [], 0
         for e in embeds_list:
             r1 = r0 + int(e.shape[0])
             # what this batch's own generate() call returns: HF stops a call as soon as all of ITS rows have finished
-            out = _trim_at_eos(st.out_ids[r0:r1], n_done, st.eos_all).clone()
+            out = _trim_at_eos(ids[r0:r1], n_done, st.eos_all).clone()
             if return_step_logits or return_hidden:
                 r = (out, sl[r0:r1, : out.shape[1]].clone())
             else:
@@ -2237,7 +2403,7 @@ class GenerationEngine:
 
     def _generate_split(self, groups, embeds, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, prefill_chunk, use_graph,
                         return_step_logits, return_hidden, return_first_logits, sampling=None, constraint=None, return_logprobs=False,
-                        processors=None):
+                        processors=None, shed=None):
         """The batch does not fit the device's memory in one piece: generate the groups one after the other (rows are independent,
         so the results are those of the one-piece run up to the kernel choice a different M implies) and join them.  A group
         that finished early (EOS) is padded to the longest group's length with pad ids, like HF pads finished rows."""
@@ -2256,7 +2422,7 @@ class GenerationEngine:
                                    return_step_logits=return_step_logits, return_hidden=return_hidden, return_first_logits=return_first_logits,
                                    sampling=reseed_sampling(sampling, 104729 * b0),
                                    constraint=constraint.rows(b0, b0 + n) if constraint is not None else None, return_logprobs=return_logprobs,
-                                   processors=processors)
+                                   processors=processors, shed=shed)
             finally:
                 self.kv_budget_bytes = saved
             parts.append(r if isinstance(r, tuple) else (r,))
@@ -2275,6 +2441,82 @@ class GenerationEngine:
                 cols.append(t)
             res.append(torch.cat(cols, 0))
         return res[0] if len(res) == 1 else tuple(res)
+
+    # ------------------------------------------------------------------ shed_finished: a wave drops its finished rows
+    @staticmethod
+    def _shed_flush(st: "_DecodeState", shed: "_Shed", step: int):
+        """The ids a state holds for its real rows after decode step `step` (columns 0 .. step are written), into the call's result buffer
+        under the rows' original indices.  The root state's flush also lays the pad id over the columns behind `step`: a row that stays
+        behind has finished, and the unshed call writes st.pad for it at every later step."""
+        if st.rows is None:
+            shed.out.copy_(st.out_ids)
+            shed.out[:, step + 1:] = st.pad
+        else:
+            shed.out[st.rows_idx] = st.out_ids[:st.n_real]
+
+    def _shed_to(self, root: "_DecodeState", st: "_DecodeState", live: List[int], Bp: int, shed: "_Shed", step: int) -> "_DecodeState":
+        """The state `st` (the wave's root state or one of its children) hands its unfinished rows `live` (ascending row indices of st) to the
+        root's child state of Bp >= len(live) rows:
+          * st's ids go to the result buffer (every row that stays behind has finished: its later columns are the buffer's pad fill);
+          * crab_kv_compact_rows moves the live cache rows to the front of every layer, in place; the child's cache is the view [:, :Bp] of
+            the root's allocation (the decode kernels take the layer stride separately);
+          * the child owns cur_ids, out_ids, finished, row_off, pos_dev, step_dev, logits, workspace and graph of its own: the live rows'
+            words are gathered into rows 0 .. n - 1, the counters copied.  Rows n .. Bp - 1 of the rung are dead fillers (finished = 1,
+            cur_ids = pad): they step over stale but valid cache rows and nothing of theirs is read back;
+          * ch.rows holds every row's index in the whole wave: sample mode keys its draws by it (_select_token), the sinks scatter by it.
+        The child is cached on the root under (Bp, weight form) with its workspace and graph - the engine's decode-workspace LRU
+        (_workspace) never sees it, so the root's own workspace and graph survive a ladder of any length - and refilled by every shed."""
+        dev = self.device
+        n = len(live)
+        self._shed_flush(st, shed, step)
+        # the one upload of a shed (the live list, before the compaction is launched): every index below is made from it on the device, so
+        # nothing here waits for the compaction
+        idx = ops.kv_compact_rows(st.kc, st.vc, live, st.pos_dev, st.row_off).to(torch.int64)
+        w8 = self._w8_rows(Bp)
+        w8_key = ("fp8_e4m3",) + tuple(t.data_ptr() for pair in self._quantized() for t in pair) if w8 else ("bf16",)
+        ch = root.children.get((Bp, w8_key))
+        if ch is None:
+            V, n_cols = self.lm_head.weight.shape[0], root.out_ids.shape[1]
+            ch = _DecodeState()
+            ch.key, ch.graph = root.key + ("shed", Bp) + w8_key, None
+            ch.B, ch.Tmax, ch.kc, ch.vc, ch.slot = Bp, root.Tmax, root.kc[:, :Bp], root.vc[:, :Bp], root.slot
+            ch.ks = ch.vs = None
+            ch.w8 = w8
+            tc, uc = self._ws_cols()
+            ch.ws = _Workspace(self.cfg, Bp, dev, tc, uc)
+            ch.lookup = None
+            ch.logits = torch.empty((Bp, V), device=dev, dtype=torch.float32)
+            ch.hn = None                                       # return_hidden is refused with the option: no step writes hidden rows
+            ch.cur_ids = torch.empty((Bp,), device=dev, dtype=torch.int64)
+            ch.out_ids = torch.empty((Bp, n_cols), device=dev, dtype=torch.int64)
+            ch.finished = torch.empty((Bp,), device=dev, dtype=torch.int32)
+            ch.pos_dev = torch.empty((1,), device=dev, dtype=torch.int32)
+            ch.step_dev = torch.empty((1,), device=dev, dtype=torch.int32)
+            ch.row_off = torch.zeros((Bp,), device=dev, dtype=torch.int32) if root.row_off is not None else None
+            ch.rows = torch.empty((Bp,), device=dev, dtype=torch.int32)
+            ch.eos, ch.pad, ch.min_new, ch.want_hidden, ch.sampling = root.eos, root.pad, root.min_new, False, root.sampling
+            ch.prefix = ch.beam = ch.trie = ch.node = ch.lp = ch.lp_norm = ch.proc = ch.cfg = ch.guided = None
+            ch.save_idx = ch.save_val = ch.stop_dev = None
+            ch.eos_all, ch.children = root.eos_all, None
+            root.children[(Bp, w8_key)] = ch
+        if w8:
+            self._w_used = "fp8_e4m3" if self._w_used != "bf16" else "bf16"
+        ch.S = st.S
+        ch.cur_ids.fill_(st.pad); ch.cur_ids[:n] = st.cur_ids[idx]
+        # columns 0 .. step are written; behind them the child holds the pad id, NOT the parent's fill (the root's buffer is filled with
+        # pad_token_id or 0, and st.pad is the EOS id when no pad_token_id was given): a row that finishes inside the child and stays behind at
+        # the next shed then carries st.pad behind its EOS into the result, as the unshed call writes it at every later step
+        ch.out_ids.fill_(st.pad); ch.out_ids[:n, :step + 1] = st.out_ids[idx, :step + 1]
+        ch.finished.fill_(1); ch.finished[:n] = st.finished[idx]
+        if ch.row_off is not None:
+            ch.row_off.zero_(); ch.row_off[:n] = st.row_off[idx]
+        ch.pos_dev.copy_(st.pos_dev); ch.step_dev.copy_(st.step_dev)
+        orig = st.rows_host if st.rows is not None else list(range(st.B))
+        ch.rows_host, ch.n_real = [orig[i] for i in live], n
+        ch.rows_idx = st.rows_idx[idx] if st.rows is not None else idx
+        ch.rows.fill_(-1); ch.rows[:n] = ch.rows_idx.to(torch.int32)
+        shed.log.append((int(step), int(st.B), int(Bp), sum(1 for j, s in enumerate(live) if s != j)))
+        return ch
 
     def _capture(self, st: "_DecodeState"):
         """Capture one decode step into a HIP graph on a side stream (torch.cuda.CUDAGraph = hipGraph on ROCm); the graph is

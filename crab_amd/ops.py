@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional
+from typing import List, Optional
 
 import torch
 
@@ -966,6 +966,74 @@ def kv_beam_reorder(kc, vc, K: int, beam_idx, finished, pos_dev, first_slot: int
     _chk_i32("pos_dev", pos_dev, 1, kc.device)
     _lib.check(_lib.load().crab_kv_beam_reorder(_lib.ctx(d), _stream(), _p(kc), _p(vc), L, rows, int(K), Hk, Tmax, hd, int(first_slot), _p(pos_dev),
                                                 _p(beam_idx), _p(finished)), d)
+
+
+COMPACT_MAX_UNITS = (1 << 31) - 1      # 16-byte units of one cache a single crab_kv_compact_rows launch spans (the entry point refuses 2^31 and more)
+
+
+def check_compact_rows(src_rows, rows: int) -> List[int]:
+    """The contract of crab_kv_compact_rows on the host, before anything is uploaded: src_rows (a Python list or CPU tensor of the surviving
+    rows' indices) is non-empty, strictly increasing, src_rows[j] >= j and every index is below `rows`.  ValueError by name otherwise."""
+    src = [int(s) for s in (src_rows.tolist() if isinstance(src_rows, torch.Tensor) else src_rows)]
+    if not src:
+        raise ValueError("src_rows is empty: kv_compact_rows needs at least one surviving row")
+    if len(src) > int(rows):
+        raise ValueError(f"src_rows has {len(src)} entries for a cache of {rows} rows")
+    for j, s in enumerate(src):
+        if j and s == src[j - 1]:
+            raise ValueError(f"src_rows[{j}] = {s} repeats src_rows[{j - 1}]: the surviving rows must be distinct (strictly increasing)")
+        if j and s < src[j - 1]:
+            raise ValueError(f"src_rows[{j}] = {s} is below src_rows[{j - 1}] = {src[j - 1]}: src_rows must be strictly increasing")
+        if s < j:
+            raise ValueError(f"src_rows[{j}] = {s} is below its destination row {j}: rows only move towards the front")
+        if s >= int(rows):
+            raise ValueError(f"src_rows[{j}] = {s} is outside the cache's {rows} rows")
+    return src
+
+
+def kv_compact_rows(kc, vc, src_rows, pos_dev, row_off=None):
+    """crab_kv_compact_rows (csrc/kv_compact.hip): the bf16 KV caches [L, rows, Hk, Tmax, d] x 2 in place, row j <- row src_rows[j] for
+    j < len(src_rows), over the slots row_off[src_rows[j]] .. pos_dev[0]; afterwards kc[:, :len(src_rows)] is the cache of the surviving rows.
+    kc / vc may be views of an allocation with more rows (only the layer stride may exceed the packed one).  src_rows: a Python list or CPU
+    tensor, checked on the host (check_compact_rows) before it is uploaded.  Returns the device copy of src_rows (int32)."""
+    if kc.dim() != 5 or kc.shape != vc.shape:
+        raise ValueError(f"k / v cache must be [L, rows, Hk, Tmax, d] tensors of one shape, got {tuple(kc.shape)} and {tuple(vc.shape)}")
+    L, rows, Hk, Tmax, hd = kc.shape
+    src = check_compact_rows(src_rows, rows)
+    d = _dev(kc)
+    _chk_bf16(kc, vc)
+    packed = (Hk * Tmax * hd, Tmax * hd, hd, 1)
+    if kc.stride()[1:] != packed or vc.stride() != kc.stride() or kc.stride(0) < rows * packed[0]:
+        raise ValueError(f"k / v cache rows must be packed (only the layer stride may be larger), got strides {kc.stride()} and {vc.stride()}")
+    _chk_i32("pos_dev", pos_dev, 1, kc.device)
+    _chk_i32("row_off", row_off, rows, kc.device)
+    src_dev = torch.tensor(src, dtype=torch.int32).to(kc.device)
+    # one launch takes fewer than 2^31 16-byte units per cache (32 GiB): a full-size wave (32 layers x 512 rows x 32 heads x ~900 slots: 120 GiB)
+    # goes layer group by layer group - the layers are independent, so the groups are the same launch on kc[l0:l1] / vc[l0:l1]
+    per_layer = kc.stride(0) // 8
+    step = max(1, min(L, COMPACT_MAX_UNITS // max(per_layer, 1)))
+    for l0 in range(0, L, step):
+        n = min(step, L - l0)
+        _lib.check(_lib.load().crab_kv_compact_rows(_lib.ctx(d), _stream(), _p(kc[l0]), _p(vc[l0]), kc.stride(0), n, rows, Hk, Tmax, hd, len(src),
+                                                    _p(src_dev), _p(row_off), _p(pos_dev)), d)
+    return src_dev
+
+
+def sample_select_rows(row_ids, logits, cur_ids, out_ids, step_dev, finished, eos_id: int, pad_id: int, min_new_tokens: int, temperature: float,
+                       top_k: int, top_p: float, seed: int, min_p: float = 0.0, epsilon_cutoff: float = 0.0, eta_cutoff: float = 0.0):
+    """crab_sample_select_rows (csrc/sample.hip): sample_select (all three further stages 0) or sample_select_warped on row r of every buffer, the
+    draw keyed by row_ids[r] (device int32 [B]: the row's index before its wave shed rows) instead of r."""
+    d = _dev(logits)
+    B, V = logits.shape
+    _chk_i32("row_ids", row_ids, B, logits.device)
+    _chk_i32("step_dev", step_dev, 1, logits.device)
+    _chk_i32("finished", finished, B, logits.device)
+    if row_ids is None:
+        raise ValueError("row_ids must be a contiguous int32 tensor")
+    _lib.check(_lib.load().crab_sample_select_rows(_lib.ctx(d), _stream(), _p(logits), logits.stride(0), B, V, _p(cur_ids), _p(out_ids),
+                                                   out_ids.stride(0), _p(step_dev), _p(finished), eos_id, pad_id, min_new_tokens, float(temperature),
+                                                   int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, float(min_p), float(epsilon_cutoff),
+                                                   float(eta_cutoff), _p(row_ids)), d)
 
 
 def advance(pos_dev, step_dev):

@@ -321,7 +321,14 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
         a modality embedding was spliced into; with inputs_embeds alone it starts empty, as HF's does.  The ids are generate()'s own under the
         decoder's bf16 margin rule; output_logits + return_dict_in_generate gives the logits of the emitted tokens.  Refused by name next to
         it: do_sample, num_beams > 1, guidance_scale, allowed_sequences, repetition_penalty / no_repeat_ngram_size, output_token_logprobs, a
-        batch of more than one row; assistant_model stays refused."""
+        batch of more than one row; assistant_model stays refused.
+        shed_finished (not an HF name; None / False: off) / shed_every: the wave stops carrying the rows that have emitted EOS
+        (GenerationEngine.generate; csrc/kv_compact.hip) - True: the default ladder of row counts, a sorted tuple: that ladder; shed_every:
+        decode steps between two looks (default: the engine's EOS check).  The result is the call's without the option, within the decoder's
+        bf16 tolerance; do_sample keeps every row's random stream.  Refused by name next to it: num_beams > 1, guidance_scale,
+        prompt_lookup_num_tokens, allowed_sequences, repetition_penalty / no_repeat_ngram_size / several eos ids, output_token_logprobs,
+        decode_streams > 1, the fp8 KV cache."""
+        shed = UnifiedForCausalLM._shed_args(self, kwargs, "generate")
         if kwargs.get("prompt_lookup_num_tokens") is not None:
             return UnifiedForCausalLM._generate_lookup(self, batch_input_ids, batch_labels, batch_X_modals, batch_task_names, kwargs)
         beams =int(kwargs.get("num_beams") or 1)
@@ -356,7 +363,7 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
                                     prefill_chunk=int(kwargs.get("prefill_chunk", 0)), use_graph=kwargs.get("use_graph", True),
                                     return_step_logits=want_logits, decode_streams=int(kwargs.get("decode_streams", 1)),
                                     return_first_logits=want_first, sampling=sampling, kv_cache_dtype=kwargs.get("kv_cache_dtype"), weight_dtype=kwargs.get("weight_dtype"),
-                                    constraint=constraint, return_logprobs=want_lp, processors=proc)
+                                    constraint=constraint, return_logprobs=want_lp, processors=proc, **shed)
         if want_logits or want_first or want_lp:
             res = list(res)
             out = type("GenerateOutput", (), {})()
@@ -544,6 +551,8 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
             if kwargs.get(k) is not None and kwargs.get(k) is not False:
                 raise NotImplementedError(f"generate_batches returns token ids only: {k} is a generate() argument")
         want_first = bool(kwargs.get("output_first_logits"))
+        # shed_finished / shed_every: as in generate(), for every ragged wave (coalesce = True; the in-flight form is refused by name)
+        shed = UnifiedForCausalLM._shed_args(self, kwargs, "generate_batches" if coalesce else "generate_batches(coalesce=False)", routed=bool(coalesce))
         self._check_generate_kwargs(kwargs, self._PROCESSOR_ARGS | UnifiedForCausalLM._WARPER_ARGS)
         sampling = self._sampling(kwargs)
         eos, proc = self._processors(kwargs)
@@ -566,7 +575,7 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
                                          min_new_tokens=int(kwargs.get("min_new_tokens", 0) or 0), use_graph=kwargs.get("use_graph", True),
                                          sampling=sampling, return_first_logits=want_first, coalesce=coalesce, max_rows=max_rows,
                                          kv_cache_dtype=kwargs.get("kv_cache_dtype"), weight_dtype=kwargs.get("weight_dtype"), constraint=constraint,
-                                         return_logprobs=want_lp, processors=proc)
+                                         return_logprobs=want_lp, processors=proc, **shed)
         return [_logprob_output(r, want_first, _stop_ids(eos, proc)) for r in res] if want_lp else res
 
     @torch.no_grad()
@@ -586,6 +595,7 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
         for k in ("output_logits", "return_dict_in_generate", "inputs_embeds"):
             if kwargs.get(k) is not None and kwargs.get(k) is not False:
                 raise NotImplementedError(f"generate_questions returns token ids only: {k} is a generate() argument")
+        UnifiedForCausalLM._shed_args(self, kwargs, "generate_questions", routed=False)
         want_first = bool(kwargs.get("output_first_logits"))
         want_lp = bool(kwargs.get("output_token_logprobs"))
         self._check_generate_kwargs(kwargs, self._PROCESSOR_ARGS | UnifiedForCausalLM._WARPER_ARGS)
@@ -655,6 +665,39 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
                                       "it would change the decoded ids, so it is refused rather than ignored")
         if "max_length" in kwargs and kwargs.get("max_length") is not None and kwargs.get("max_new_tokens") is None:
             raise NotImplementedError("generate(max_length=...): with inputs_embeds only HF counts new tokens alone - pass max_new_tokens")
+
+    @staticmethod
+    def _shed_args(self, kwargs, entry: str = "generate", routed: bool = True):
+        """shed_finished / shed_every (not HF names; GenerationEngine.generate: a wave stops carrying the rows that have emitted EOS) -> the
+        keyword arguments the engine call gains: {} when the option is off (None / False), so that call is the call without it.  A static
+        method with an explicit self: generate() calls it on whatever object stands in for the model.  Refused by name before any device work:
+        routed = False (entry points that decode through a path without the option), and next to num_beams > 1, guidance_scale,
+        prompt_lookup_num_tokens, allowed_sequences, repetition_penalty / no_repeat_ngram_size / several eos ids, output_token_logprobs and
+        the fp8 KV cache - each owns per-row device state that a shed would have to move as well."""
+        from .decoder import shed_ladder
+        sf = kwargs.get("shed_finished")
+        if shed_ladder(sf) is None:
+            return {}
+        if not routed:
+            raise NotImplementedError(f"{entry}(shed_finished={sf!r}): not implemented on this path (generate() and generate_batches(coalesce=True) shed finished rows)")
+        neutral = {"num_beams": 1, "guidance_scale": 1.0, "prompt_lookup_num_tokens": None, "allowed_sequences": None, "allowed_set": None,
+                   "repetition_penalty": 1.0, "no_repeat_ngram_size": 0, "output_token_logprobs": False}
+        for k, off in neutral.items():
+            v = kwargs.get(k)
+            if v is None or v == off or (isinstance(off, bool) and not v):
+                continue
+            raise NotImplementedError(f"{entry}(shed_finished={sf!r}, {k}={v!r}): not implemented with shed_finished (greedy and do_sample with "
+                                      "min_new_tokens, one eos_token_id, output_logits and output_first_logits are)")
+        eos = kwargs.get("eos_token_id", self.config.eos_token_id)
+        if torch.is_tensor(eos):
+            eos = eos.reshape(-1).tolist()
+        if isinstance(eos, (list, tuple)) and len(set(int(e) for e in eos)) > 1:
+            raise NotImplementedError(f"{entry}(shed_finished={sf!r}, eos_token_id={list(eos)}): a shedding call stops on ONE eos_token_id")
+        kv = kwargs.get("kv_cache_dtype") or getattr(self._engine, "kv_cache_dtype", "bf16")
+        if kv == "fp8_e4m3":
+            raise NotImplementedError(f'{entry}(shed_finished={sf!r}) with kv_cache_dtype="fp8_e4m3": the rows of the bf16 KV cache are moved (the fp8 '
+                                      "row scales would have to move too)")
+        return {"shed_finished": sf, "shed_every": kwargs.get("shed_every")}
 
     def _processors(self, kwargs):
         """repetition_penalty / no_repeat_ngram_size / eos_token_id -> (the engine's ONE eos_token_id, its processors triple or None).  A
@@ -778,6 +821,7 @@ class UnifiedForCausalLM(nn.Module, UnifiedMetaForCausalLM):
 
     def _avs_generate(self, samples, max_rows, kwargs):
         """First half of generate_avs_many: inputs of every call (multi-scale CLIP features kept) and the ragged decode with per-step hidden states."""
+        UnifiedForCausalLM._shed_args(self, kwargs, "generate_avs", routed=False)      # the hidden rows are kept per row of the wave
         self._check_generate_kwargs(kwargs, self._PROCESSOR_ARGS | UnifiedForCausalLM._WARPER_ARGS)
         sampling = self._sampling(kwargs)
         eos, proc = self._processors(kwargs)

@@ -434,6 +434,16 @@ int crab_sample_select_warped(crab_ctx* ctx, void* stream, const float* logits, 
                               int64_t* out_ids, int64_t ld_out, const int32_t* step_dev, int32_t* finished, int eos_id, int pad_id,
                               int min_new_tokens, float temperature, int top_k, float top_p, uint64_t seed, float min_p,
                               float epsilon_cutoff, float eta_cutoff, int32_t* kept_n, float* kept_min);
+/* crab_sample_select / crab_sample_select_warped for the rows of a COMPACTED wave (crab_kv_compact_rows below): row r of every buffer is
+ * handled as in those two, but its draw is keyed by (seed, step_dev[0], row_ids[r]) - row_ids (device int32 [B]) holds the index every row had
+ * before finished rows were shed, so a row's random stream does not depend on which rows left.  With min_p, epsilon_cutoff and eta_cutoff all 0
+ * the plain kernel's operations run, else the warped ones: given the same logits row and row_ids[r] = b, the words written for row r equal
+ * those crab_sample_select / crab_sample_select_warped write for row b, bit for bit.  CRAB_E_INVALID as crab_sample_select_warped, and for a
+ * null row_ids.  ADDED under ABI 13 (crab_abi_version() still returns 13); probe for the symbol. */
+int crab_sample_select_rows(crab_ctx* ctx, void* stream, const float* logits, int64_t ldl, int B, int V, int64_t* cur_ids, int64_t* out_ids,
+                            int64_t ld_out, const int32_t* step_dev, int32_t* finished, int eos_id, int pad_id, int min_new_tokens,
+                            float temperature, int top_k, float top_p, uint64_t seed, float min_p, float epsilon_cutoff, float eta_cutoff,
+                            const int32_t* row_ids);
 /* The same step CONSTRAINED to a closed set of answers (csrc/constrain.hip): what HF does with PrefixConstrainedLogitsProcessor
  * (generation/logits_process.py: every token prefix_allowed_tokens_fn does not return is set to -inf) - without the host callback, which cannot run
  * between two replays of a captured step.  The answers are a token trie in CSR form (crab_amd/constrain.py): node n has the out-edges
@@ -544,6 +554,20 @@ int crab_beam_merge(crab_ctx* ctx, void* stream, const float* cand_score, const 
                     int32_t* hyp_fin, int32_t* unsat, int64_t* cur_ids, int32_t* beam_idx, int32_t* finished);
 int crab_kv_beam_reorder(crab_ctx* ctx, void* stream, void* k_cache, void* v_cache, int L, int rows, int num_beams, int Hk, int Tmax,
                          int head_dim, int first_slot, const int32_t* pos_dev, const int32_t* beam_idx, const int32_t* finished);
+/* In-place KV row compaction (csrc/kv_compact.hip): the live rows of a decode wave move to the front of every layer of the bf16 caches
+ * [L, rows, Hk, Tmax, head_dim] x 2, after which the first n_live rows of every layer are the cache of an n_live-row state (the decode kernels
+ * take the layer stride separately).  layer_stride: ELEMENTS between two layers (the caches may be views of an allocation with more rows).
+ *     for j = 0 .. n_live - 1: row j <- row src_rows[j], over the slots row_off[src_rows[j]] .. pos_dev[0] (inclusive, as crab_kv_beam_reorder),
+ *     every layer and KV head.  row_off (indexed by the SOURCE row) may be null: from slot 0.  More slots of a row may be copied than required;
+ *     rows >= n_live and slots > pos_dev[0] never change.
+ * Contract: src_rows (device int32 [n_live]) is strictly increasing with src_rows[j] >= j.  One thread owns a 16-byte position and walks the
+ * rows in ascending j in batches (load, then store), which under the contract never overwrites a source that is still needed: no second cache.
+ * Device indices are clamped (pos against Tmax, src_rows against rows, row_off against pos): corrupt arrays give a wrong cache, never an
+ * out-of-range access.  CRAB_E_INVALID: null operands (row_off excepted), L / rows / Hk / Tmax < 1, n_live outside 1 .. rows, head_dim not a
+ * multiple of 8, caches not 16-byte aligned, layer_stride not a multiple of 8 or below rows Hk Tmax head_dim.  CRAB_E_UNSUPPORTED: 2^31 or more
+ * 16-byte units per cache.  ADDED under ABI 13 (crab_abi_version() still returns 13); probe for the symbol. */
+int crab_kv_compact_rows(crab_ctx* ctx, void* stream, void* k_cache, void* v_cache, int64_t layer_stride, int L, int rows, int Hk, int Tmax,
+                         int head_dim, int n_live, const int32_t* src_rows, const int32_t* row_off, const int32_t* pos_dev);
 /* Classifier-free guidance of the step (csrc/cfg.hip): HF's UnbatchedClassifierFreeGuidanceLogitsProcessor without its second model forward
  * from a host callback.  The conditional and the unconditional prompt of a clip decode as two rows of one ragged batch: pair b < B is row b
  * (conditional, c) and row B + b (unconditional, u) of the raw fp32 logits [2B, V].
