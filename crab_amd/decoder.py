@@ -14,6 +14,7 @@ token position, step index and finished flags live in device memory, so there is
 from __future__ import annotations
 
 import contextlib
+import dataclasses
 import math
 import types
 from dataclasses import dataclass
@@ -38,7 +39,9 @@ W8_MAX_ROWS = 16                            # rows up to which a decode step str
 KV_CACHE_DTYPES = ("bf16", "fp8_e4m3")     # GenerationEngine(kv_cache_dtype=...): the default bf16 cache | the opt-in FP8 (OCP e4m3fn) cache with fp32 row scales
 SHED_MIN_STEPS_LEFT = 4   # shed_finished: a look sheds only while at least this many decode steps remain (the measured break-even is ~3 steps)
 EOS_CHECK_EVERY = 16      # decode steps between two host reads of the `finished` flags: the only synchronisation inside the step loop (_run_steps)
-NATIVE_LAYERS = True      # False: issue every launch of a layer from Python (A/B runs and the sequencer-equivalence tests)
+ONE_EOS = ("the device-resident decode loop stops on ONE id (pass the chat end token, e.g. <|im_end|>; the reference's own Qwen path never reaches HF "
+           "generate, SURVEY.md 2); further stop ids go into processors = (repetition_penalty, no_repeat_ngram_size, stop_token_ids)")      # one_eos: what generate() says
+NATIVE_LAYERS = True     # False: issue every launch of a layer from Python (A/B runs and the sequencer-equivalence tests)
 
 
 @dataclass
@@ -358,6 +361,107 @@ def _pack_waves(Bs: List[int], cap: int) -> List[List[int]]:
     return waves
 
 
+def one_eos(eos_token_id, what: str):
+    """HF accepts a list of stop ids (Qwen2-7B-Instruct's generation_config holds two); the device loop carries ONE: a list of one distinct id
+    is that id, an empty list is None, several ids are refused - `what` is the caller's half of the message.  THE rule of every entry point."""
+    if not isinstance(eos_token_id, (list, tuple)):
+        return eos_token_id
+    if len(set(int(e) for e in eos_token_id)) > 1:
+        raise NotImplementedError(f"eos_token_id = {list(eos_token_id)}: {what}")
+    return eos_token_id[0] if len(eos_token_id) else None
+
+
+@dataclass(frozen=True)
+class _Request:
+    """The per-call options of a generate entry point, normalised ONCE by it (after its check_* / normalize_* calls): every private method takes
+    (tensors ..., req) and what is genuinely its own.  eos: the single stop id (one_eos) or None; pad_token_id: as given; shed: the call's
+    _Shed.  The last four fields vary per wave or group of a call, through replace(): the wave's _Constraint, cfg = (guidance_scale, pairs),
+    lookup = (k, max_ngram, keep step logits), extra_key = what else the captured step bakes in (prefix buffers, beam parameters).
+    A new option is a field here, a term of _state_key, a line of _Collect if it returns something, and its launch in _select / _decode_step."""
+    max_new_tokens: int
+    eos: Optional[int] = None
+    pad_token_id: Optional[int] = None
+    min_new_tokens: int = 0
+    use_graph: bool = True
+    sampling: Optional[tuple] = None
+    processors: Optional[tuple] = None
+    return_step_logits: bool = False
+    return_hidden: bool = False
+    return_first_logits: bool = False
+    return_logprobs: bool = False
+    prefill_chunk: int = 0
+    shed: Optional[_Shed] = None
+    constraint: Optional["_Constraint"] = None
+    cfg: Optional[tuple] = None
+    lookup: Optional[tuple] = None
+    extra_key: tuple = ()
+
+    replace = dataclasses.replace                # the per-wave variation: req.replace(sampling=..., constraint=..., cfg=..., extra_key=...)
+
+    @property
+    def graphed(self) -> bool:                   # the steps are captured and replayed: with one or two tokens there is none (or one) to replay
+        return bool(self.use_graph and self.max_new_tokens > 2)
+
+    @property
+    def join_pad(self) -> int:
+        """What fills the ids of a group or wave that stopped before the longest (_join): pad -> eos -> 0.  NOT a state's pad word (stop_words),
+        which also falls back to the first further stop id: that is what a finished row emits INSIDE the step (HF's list-valued eos_token_id
+        makes its first id the pad); a join fills columns behind a whole group's end, and has always stopped at eos."""
+        return int(self.pad_token_id) if self.pad_token_id is not None else (int(self.eos) if self.eos is not None else 0)
+
+    def rows(self, b0: int, b1: int) -> "_Request":
+        """The request of rows b0 .. b1 of the call's batch: the constraint's roots of those rows."""
+        return self if self.constraint is None else self.replace(constraint=self.constraint.rows(b0, b1))
+
+
+def stop_words(eos, pad_token_id, processors):
+    """(eos, proc, pad) as a decode state holds them.  eos: -1 for None.  proc: the triple normalised against eos - a stop id equal to eos is
+    the select's own, and a triple that is neutral after that is None: the call meets the key, graph and launches of a call without it.
+    pad: what a finished row emits - pad_token_id, else eos, else the first further stop id (HF: the first id of a list-valued eos), else 0."""
+    eos = -1 if eos is None else int(eos)
+    proc = normalize_processors(processors)
+    if proc is not None:
+        proc = normalize_processors((proc[0], proc[1], tuple(e for e in proc[2] if e != eos)))
+    stops = proc[2] if proc is not None else ()
+    pad = int(pad_token_id) if pad_token_id is not None else (eos if eos >= 0 else (stops[0] if stops else 0))
+    return eos, proc, pad
+
+
+def _state_key(B, Tmax, max_new_tokens, eos, pad, min_new_tokens, return_hidden, ptrs, lora, sampling, ragged, kv_mode, scale_ptrs, w8_key,
+               logprobs, extra_key=(), trie_key=(), proc=None, cfg=None, lookup=None, S=0):
+    """The key of a decode state: everything its captured HIP graph bakes in, as plain values - a state (and its graph) serves exactly the
+    calls whose key is equal.  ptrs: K cache, V cache, id of the workspace, RoPE table, lm_head, embedding, first q|k|v weight, as ints;
+    scale_ptrs: the FP8 cache's two row-scale pointers (0, 0 in bf16 mode); w8_key: _w8_key; eos / pad / proc: stop_words; S: with lookup only."""
+    return (B, Tmax, max_new_tokens, eos, pad, int(min_new_tokens), bool(return_hidden)) + tuple(ptrs) + \
+        (bool(lora), sampling, bool(ragged), kv_mode) + tuple(scale_ptrs) + (w8_key, bool(logprobs)) + tuple(extra_key) + tuple(trie_key) + \
+        (("proc",) + proc if proc is not None else ()) + \
+        (("cfg", float(cfg[0]), int(cfg[1])) if cfg is not None else ()) + \
+        (("lookup", int(lookup[0]), int(lookup[1]), bool(lookup[2]), int(S)) if lookup is not None else ())
+
+
+def _child_key(root_key, Bp: int, w8_key):
+    """The Bp-row child of a wave that sheds rows (_shed_to): the root's key stands for all the child bakes in but its rows and weight form."""
+    return tuple(root_key) + ("shed", Bp) + tuple(w8_key)
+
+
+def _join(parts, pad: int, keep=None):
+    """Groups or waves of one call that ran one after the other, joined along the rows (parts[i]: the tuple of tensors of part i).  A part that
+    stopped early (EOS) is widened to the longest: its ids (element 0) with `pad`, its per-step tensors with zeros; never element `keep`
+    (the first logits [B, V]: no step axis)."""
+    n_max = max(q[0].shape[1] for q in parts)
+    res = []
+    for j in range(len(parts[0])):
+        cols = []
+        for q in parts:
+            t = q[j]
+            if j != keep and t.dim() >= 2 and t.shape[1] < n_max:
+                fill = torch.full((t.shape[0], n_max - t.shape[1]) + tuple(t.shape[2:]), pad if j == 0 else 0, device=t.device, dtype=t.dtype)
+                t = torch.cat([t, fill], 1)
+            cols.append(t)
+        res.append(torch.cat(cols, 0))
+    return tuple(res)
+
+
 class GenerationEngine:
     """Prefill + greedy decode over a DecoderModel + lm_head.  Owns KV caches / workspaces (torch allocator)."""
 
@@ -429,6 +533,11 @@ class GenerationEngine:
         """True when a decode step of B rows streams the FP8 weights under the mode that holds."""
         return getattr(self, "_w_mode", "bf16") == "fp8_e4m3" and B <= W8_MAX_ROWS
 
+    def _w8_key(self, B: int) -> tuple:
+        """The weight form of a B-row decode step as a state key holds it: ("bf16",), or the mode and the pointers of every group's codes and
+        row scales - the FP8 forms are (re)built here (_quantized), which has to happen before a step can be captured."""
+        return ("fp8_e4m3",) + tuple(t.data_ptr() for pair in self._quantized() for t in pair) if self._w8_rows(B) else ("bf16",)
+
     def _with_kv_mode(self, kv_cache_dtype, fn, *a, **k):
         """Run fn under the per-call mode (None: whatever holds - the engine's, or the enclosing call's for the calls generate() makes itself)."""
         if kv_cache_dtype is None:
@@ -439,22 +548,31 @@ class GenerationEngine:
         finally:
             self._kv_mode = saved
 
-    def _call(self, kv_cache_dtype, weight_dtype, fn, *a, **k):
-        """The one entry of generate() / generate_many(): fn under both per-call modes (both values are checked before either is set, so a
+    def _call(self, kv_cache_dtype, weight_dtype, shed, fn, *a):
+        """The one entry of every generate method: fn under both per-call modes (both values are checked before either is set, so a
         refused call changes nothing) and under the one retry (_retry_after_eviction), then last_plan is stamped with the weight dtype the
         call's decode states ran with ("bf16" when a decode batch exceeded 16 rows).  Nothing inside the engine comes back here - a single
         batch of generate_many, a lone coalesced wave and the groups of a split batch call _generate - so there is one verdict and one retry
-        per call by construction."""
+        per call by construction.  shed: the _Shed of a shedding call (the one its request carries) or None - every attempt starts its
+        record again (a retry after an eviction runs the call anew), and last_plan is stamped with what it recorded."""
         if kv_cache_dtype is not None:
             self.check_kv_cache_dtype(kv_cache_dtype)
         saved = self._w_mode
         if weight_dtype is not None:
             self._w_mode = self.check_weight_dtype(weight_dtype)
         self._w_used = None
+
+        def run():
+            if shed is not None:
+                shed.log, shed.captures = [], 0
+            return fn(*a)
+
         try:
-            res = self._with_kv_mode(kv_cache_dtype, self._retry_after_eviction, fn, *a, **k)
+            res = self._with_kv_mode(kv_cache_dtype, self._retry_after_eviction, run)
             if isinstance(self.last_plan, dict):
                 self.last_plan["weight_dtype_used"] = self._w_used or "bf16"
+                if shed is not None:
+                    self.last_plan["shed"], self.last_plan["shed_captures"] = list(shed.log), shed.captures
             return res
         finally:
             self._w_mode = saved
@@ -1274,7 +1392,7 @@ class GenerationEngine:
                                    st.finished, st.eos, st.pad, st.min_new, t, k, p_, seed + 7919 * st.slot)
         elif st.sampling is None:
             ops.greedy_select(logits, st.cur_ids, st.out_ids, st.step_dev, st.finished, st.eos, st.pad, st.min_new)
-        elif getattr(st, "rows", None) is not None:
+        elif st.rows is not None:
             # the child state of a wave that shed rows (_shed_to): every row draws under the index it had in the whole wave, so the random
             # stream is the unshed call's; one entry for both tuple forms (it picks the plain or the warped pipeline itself)
             t, k, p_, seed = st.sampling[:4]
@@ -1289,16 +1407,15 @@ class GenerationEngine:
             ops.sample_select_warped(logits, st.cur_ids, st.out_ids, st.step_dev, st.finished, st.eos, st.pad, st.min_new, t, k, p_,
                                      seed + 7919 * st.slot, min_p, eps, eta)
 
-    def _state(self, B: int, S: int, max_new_tokens: int, eos_token_id, pad_token_id, min_new_tokens: int, return_hidden: bool, slot: int,
-               sampling=None, ragged: bool = False, extra_key=(), constraint=None, logprobs: bool = False, processors=None,
-               cfg=None, lookup=None) -> "_DecodeState":
+    def _state(self, B: int, S: int, req: _Request, slot: int = 0, ragged: bool = False) -> "_DecodeState":
         """The persistent decode state of `slot` for B sequences whose (longest) prompt has S rows: KV cache, per-row words, logits and the HIP
-        graph captured over them.  Kept per slot and reused by every call whose shapes, flags and buffers are the same: the key holds
-        everything the captured launches bake in (pointers included).  ragged: the state of a coalesced batch (generate_many(coalesce=True)) -
-        it owns a row_off word per row (first cache slot of the row's sequence) that the captured decode step reads.  extra_key: what else a caller's captured step bakes in
+        graph captured over them.  Kept per slot and reused by every call whose shapes, flags and buffers are the same: the key (_state_key)
+        holds everything the captured launches bake in (pointers included).  ragged: the state of a coalesced batch
+        (generate_many(coalesce=True)) - it owns a row_off word per row (first cache slot of the row's sequence) that the captured decode step
+        reads.  The fields of `req` it reads, beside the plain ones:  extra_key: what else a caller's captured step bakes in
         (generate_shared_prefix: the prefix cache, its length, the tile plan and the workspace).  constraint: the rows' _Constraint (closed-set
         generation) - the trie's device pointers enter the key, so a captured graph never crosses tries, and every call puts the rows back on
-        their roots.  logprobs: the state owns st.lp [2, B, max_new_tokens] fp32 (plane 0: log-probability of every emitted token over the
+        their roots.  return_logprobs: the state owns st.lp [2, B, max_new_tokens] fp32 (plane 0: log-probability of every emitted token over the
         whole vocabulary, plane 1: within the allowed set; zeroed by every call like out_ids) and st.lp_norm [B, 4], and _select fills them;
         the flag is part of the key, so a graph captured without the two launches is never replayed for a call that wants them.
         processors: (repetition_penalty, no_repeat_ngram_size, stop_token_ids) or None - a non-neutral triple owns st.save_idx / st.save_val
@@ -1313,85 +1430,66 @@ class GenerationEngine:
         (_Lookup: history, draft ids, counters).  All three values enter the key, and so does S: the history is sized S + max_new_tokens and the
         captured draft / accept launches bake S in as a host integer (a plain state meets S only through pos_dev; Tmax alone would let two
         prompt lengths of one 64-row bucket share a state)."""
+        max_new_tokens, constraint, cfg, lookup = req.max_new_tokens, req.constraint, req.cfg, req.lookup
         if int(max_new_tokens) < 1:                             # HF: GenerationConfig.validate() - "`max_new_tokens` must be greater than 0"; here the first token's slot would not exist
             raise ValueError(f"`max_new_tokens` must be greater than 0, but is {max_new_tokens}.")
         dev = self.device
-        D = self.cfg.hidden_size
         lk_rows = (int(lookup[0]) + 1) if lookup is not None else 1
         Tmax = _round_up(S + max_new_tokens + lk_rows - 1, 64)
         kv = self.alloc_cache(B, Tmax, slot=slot)
         kc, vc = kv[0], kv[1]
         ks, vs = (kv[2], kv[3]) if len(kv) == 4 else (None, None)          # fp8 mode: the row scales beside the codes
         V = self.lm_head.weight.shape[0]
-        if isinstance(eos_token_id, (list, tuple)):            # HF accepts a list of stop ids (Qwen2-7B-Instruct's generation_config holds two); the device loop carries one
-            if len(set(int(e) for e in eos_token_id)) > 1:
-                raise NotImplementedError(f"eos_token_id = {list(eos_token_id)}: the device-resident decode loop stops on ONE id (pass the chat end token, e.g. "
-                                          "<|im_end|>; the reference's own Qwen path never reaches HF generate, SURVEY.md 2); further stop ids go "
-                                          "into processors = (repetition_penalty, no_repeat_ngram_size, stop_token_ids)")
-            eos_token_id = eos_token_id[0] if len(eos_token_id) else None
-        eos = -1 if eos_token_id is None else int(eos_token_id)
-        # processors, normalised BEFORE the key is built: a stop id equal to eos_token_id is the select's own, and a triple that is neutral
-        # after that is no triple - the call then meets the key, the graph and the launches of a call without it
-        proc = normalize_processors(processors)
-        if proc is not None:
-            proc = normalize_processors((proc[0], proc[1], tuple(e for e in proc[2] if e != eos)))
+        # the pad word falls back to the first further stop id as well (stop_words): NOT _Request.join_pad, which says why the two differ
+        eos, proc, pad = stop_words(req.eos, req.pad_token_id, req.processors)
         stops = proc[2] if proc is not None else ()
         if proc is not None and int(max_new_tokens) > ops.LOGITS_PROC_MAX_STEPS:
             raise NotImplementedError(f"processors with max_new_tokens = {max_new_tokens}: crab_logits_edit holds at most {ops.LOGITS_PROC_MAX_STEPS} generated tokens")
-        pad = int(pad_token_id) if pad_token_id is not None else (eos if eos >= 0 else (stops[0] if stops else 0))
         ws = self._workspace(B * lk_rows, slot, decode=True)
         tab = self._rope_tab(Tmax)
         # the weight mode of this state's decode steps; the FP8 forms are (re)built here, before any capture, and their pointers enter the key
-        w8 = self._w8_rows(B)
-        w8_key = ("fp8_e4m3",) + tuple(t.data_ptr() for pair in self._quantized() for t in pair) if w8 else ("bf16",)
+        w8, w8_key = self._w8_rows(B), self._w8_key(B)
         self._w_used = "bf16" if (not w8 or self._w_used == "bf16") else "fp8_e4m3"
-        key = (B, Tmax, max_new_tokens, eos, pad, int(min_new_tokens), bool(return_hidden), kc.data_ptr(), vc.data_ptr(), id(ws),
-               tab.data_ptr(), self.lm_head.weight.data_ptr(), self.model.embed_tokens.weight.data_ptr(),
-               self.model.layers[0].self_attn._qkv.W.data_ptr(),
-               self.model.layers[0].self_attn._qkv.RA is not None, sampling, bool(ragged),
-               self._kv_mode, ks.data_ptr() if ks is not None else 0, vs.data_ptr() if vs is not None else 0, w8_key, bool(logprobs)) + tuple(extra_key) + \
-            (constraint.dev.key if constraint is not None else ()) + (("proc",) + proc if proc is not None else ()) + \
-            (("cfg", float(cfg[0]), int(cfg[1])) if cfg is not None else ()) + \
-            (("lookup", int(lookup[0]), int(lookup[1]), bool(lookup[2]), int(S)) if lookup is not None else ())
+        qkv0 = self.model.layers[0].self_attn._qkv
+        key = _state_key(B, Tmax, max_new_tokens, eos, pad, req.min_new_tokens, req.return_hidden,
+                         (kc.data_ptr(), vc.data_ptr(), id(ws), tab.data_ptr(), self.lm_head.weight.data_ptr(),
+                          self.model.embed_tokens.weight.data_ptr(), qkv0.W.data_ptr()), qkv0.RA is not None, req.sampling, ragged, self._kv_mode,
+                         (ks.data_ptr(), vs.data_ptr()) if ks is not None else (0, 0), w8_key, req.return_logprobs, req.extra_key,
+                         constraint.dev.key if constraint is not None else (), proc, cfg, lookup, S)
         st = self._dec.get(slot)
         if st is None or st.key != key:
             st = _DecodeState()
-            st.key, st.graph = key, None
+            st.key = key
             st.B, st.Tmax, st.kc, st.vc, st.slot, st.ws = B, Tmax, kc, vc, slot, ws
             st.ks, st.vs = ks, vs
             st.w8 = w8
-            st.lookup = _Lookup(dev, S, int(max_new_tokens), int(lookup[0]), int(lookup[1]), V, bool(lookup[2])) if lookup is not None else None
-            st.logits = torch.empty((B, V), device=dev, dtype=torch.float32) if lookup is None else st.lookup.logits[:B]
-            st.hn = torch.empty((B, D), device=dev, dtype=BF16)
-            st.cur_ids = torch.empty((B,), device=dev, dtype=torch.int64)
-            st.out_ids = torch.empty((B, max_new_tokens), device=dev, dtype=torch.int64)
-            st.finished = torch.empty((B,), device=dev, dtype=torch.int32)
-            st.pos_dev = torch.empty((1,), device=dev, dtype=torch.int32)
-            st.step_dev = torch.empty((1,), device=dev, dtype=torch.int32)
-            st.row_off = torch.zeros((B,), device=dev, dtype=torch.int32) if ragged else None
-            st.eos, st.pad, st.min_new, st.want_hidden = eos, pad, int(min_new_tokens), bool(return_hidden)
-            st.sampling = sampling
-            st.prefix = None
-            st.beam = None                                     # generate_beam: the ops.BeamState born with the state (its parameters are in extra_key)
-            st.trie = constraint.dev if constraint is not None else None
-            st.node = torch.empty((B,), device=dev, dtype=torch.int32) if constraint is not None else None
-            st.lp = torch.empty((2, B, max_new_tokens), device=dev, dtype=torch.float32) if logprobs else None
-            st.lp_norm = torch.zeros((B, 4), device=dev, dtype=torch.float32) if logprobs else None
+            if lookup is not None:
+                st.lookup = _Lookup(dev, S, int(max_new_tokens), int(lookup[0]), int(lookup[1]), V, bool(lookup[2]))
+            st.alloc(dev, B, max_new_tokens, V, ragged, logits=st.lookup.logits[:B] if lookup is not None else None)
+            st.hn = torch.empty((B, self.cfg.hidden_size), device=dev, dtype=BF16)
+            st.eos, st.pad, st.min_new, st.want_hidden = eos, pad, int(req.min_new_tokens), bool(req.return_hidden)
+            st.sampling = req.sampling
+            if constraint is not None:
+                st.trie, st.node = constraint.dev, torch.empty((B,), device=dev, dtype=torch.int32)
+            if req.return_logprobs:
+                st.lp = torch.empty((2, B, max_new_tokens), device=dev, dtype=torch.float32)
+                st.lp_norm = torch.zeros((B, 4), device=dev, dtype=torch.float32)
             # processors: the save area of crab_logits_edit / crab_logits_restore and the device copy of the further stop ids.  The buffers are
             # born with the state and die with it, so the values in the key stand for their pointers as well
             st.proc, st.eos_all = proc, (eos,) + stops
-            n_slots = 2 * int(max_new_tokens) + len(stops)
-            st.save_idx = torch.full((B, n_slots), -1, device=dev, dtype=torch.int32) if proc is not None else None
-            st.save_val = torch.zeros((B, n_slots), device=dev, dtype=torch.float32) if proc is not None else None
+            if proc is not None:
+                n_slots = 2 * int(max_new_tokens) + len(stops)
+                st.save_idx = torch.full((B, n_slots), -1, device=dev, dtype=torch.int32)
+                st.save_val = torch.zeros((B, n_slots), device=dev, dtype=torch.float32)
             st.stop_dev = torch.tensor(stops, dtype=torch.int32).to(dev) if stops else None
-            st.cfg = (float(cfg[0]), int(cfg[1])) if cfg is not None else None
-            st.guided = torch.empty((int(cfg[1]), V), device=dev, dtype=torch.float32) if cfg is not None else None
+            if cfg is not None:
+                st.cfg, st.guided = (float(cfg[0]), int(cfg[1])), torch.empty((int(cfg[1]), V), device=dev, dtype=torch.float32)
             # shed_finished: the child states of this state, (rows, weight form) -> _DecodeState (_shed_to).  They live and die with their
             # parent - its key stands for everything theirs bake in - so invalidate() and a changed key drop them with it
-            st.rows, st.children = None, {}
+            st.children = {}
             self._dec[slot] = st
         st.S = S
-        st.cur_ids.zero_(); st.out_ids.fill_(pad_token_id if pad_token_id is not None else 0); st.finished.zero_()
+        st.cur_ids.zero_(); st.out_ids.fill_(req.pad_token_id if req.pad_token_id is not None else 0); st.finished.zero_()
         st.pos_dev.fill_(S - 1); st.step_dev.zero_()
         if st.lp is not None:
             st.lp.zero_()
@@ -1416,14 +1514,12 @@ class GenerationEngine:
         self.prefill(emb, sk, sv, b0=0, logits_out=lo, hn_out=hn, pos_ids=pos_ids, kv_start=kv_start)
         ops.kv_quant_fp8(sk, sv, st.kc, st.vc, st.ks, st.vs, b0=b0, t0=0, t_dst=t0, S=S, row_off=kv_start)
 
-    def _start(self, embeds: torch.Tensor, max_new_tokens: int, eos_token_id, pad_token_id, min_new_tokens: int, prefill_chunk: int,
-               return_hidden: bool, slot: int, sink=None, sampling=None, constraint=None, logprobs: bool = False, processors=None,
-               lookup=None) -> "_DecodeState":
+    def _start(self, embeds: torch.Tensor, req: _Request, slot: int = 0, sink=None) -> "_DecodeState":
         """Allocate the decode state of one group of sequences, prefill it and select its first token."""
         B, S, D = embeds.shape
-        st = self._state(B, S, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, return_hidden, slot, sampling, constraint=constraint,
-                         logprobs=logprobs, processors=processors, lookup=lookup)
+        st = self._state(B, S, req, slot)
         # ---- prefill in chunks of sequences (bounds activation memory, keeps GEMM M in the MFMA-efficient range)
+        prefill_chunk = req.prefill_chunk
         chunks = self.plan_prefill_chunks(B, S) if not prefill_chunk else [prefill_chunk] * (B // prefill_chunk) + \
             ([B % prefill_chunk] if B % prefill_chunk else [])
         b0 = 0
@@ -1467,9 +1563,7 @@ class GenerationEngine:
             b0 += n_span
             g = g1 + 1
 
-    def _start_ragged(self, embeds_list: List[torch.Tensor], max_new_tokens: int, eos_token_id, pad_token_id, min_new_tokens: int,
-                      sink=None, sampling=None, return_hidden: bool = False, constraint=None, logprobs: bool = False, processors=None,
-                      cfg=None) -> "_DecodeState":
+    def _start_ragged(self, embeds_list: List[torch.Tensor], req: _Request, sink=None) -> "_DecodeState":
         """The decode state of SEVERAL generate() calls coalesced into one batch.  Group g = [B_g, S_g, D] is one call of the eval loop: its
         own prompt length and left padding, positions 0 .. S_g - 1 (unified_llama.py:262-267).  All rows share one KV cache [L, sum B_g, Hk,
         Tmax, d] in which every group is RIGHT-ALIGNED at Smax = max S_g: group g's prompt occupies slots Smax - S_g .. Smax - 1, so the token
@@ -1481,8 +1575,7 @@ class GenerationEngine:
         Bs = [int(e.shape[0]) for e in embeds_list]
         Ss = [int(e.shape[1]) for e in embeds_list]
         Bt, Smax = sum(Bs), max(Ss)
-        st = self._state(Bt, Smax, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, return_hidden, 0, sampling, ragged=True,
-                         constraint=constraint, logprobs=logprobs, processors=processors, cfg=cfg)
+        st = self._state(Bt, Smax, req, 0, ragged=True)
         st.row_off.copy_(torch.tensor([Smax - S for B, S in zip(Bs, Ss) for _ in range(B)], dtype=torch.int32), non_blocking=False)
         waste = sum(B * (Smax - S) for B, S in zip(Bs, Ss)) / max(1, sum(B * S for B, S in zip(Bs, Ss)))
         if len(set(Ss)) > 1 and waste <= RAGGED_PAD_MAX:
@@ -1568,32 +1661,13 @@ class GenerationEngine:
         plan = check_shed(shed_finished, shed_every, constraint, proc, return_logprobs, return_hidden, decode_streams,
                           self._kv_mode if kv_cache_dtype is None else self.check_kv_cache_dtype(kv_cache_dtype))
         cons, = self._constraints(constraint, [int(embeds.shape[0])], eos_token_id, min_new_tokens, flat=True)
-        if plan is not None:
-            return self._call_shedding(plan, kv_cache_dtype, weight_dtype, self._generate, embeds, max_new_tokens, eos_token_id, pad_token_id,
-                                       min_new_tokens, prefill_chunk, use_graph, return_step_logits, return_hidden, decode_streams,
-                                       return_first_logits, sampling, cons, return_logprobs, processors=proc)
-        return self._call(kv_cache_dtype, weight_dtype, self._generate, embeds, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens,
-                          prefill_chunk, use_graph, return_step_logits, return_hidden, decode_streams, return_first_logits, sampling, cons,
-                          return_logprobs, processors=proc)
+        req = _Request(max_new_tokens, one_eos(eos_token_id, ONE_EOS), pad_token_id, min_new_tokens, use_graph, sampling, proc, return_step_logits,
+                       return_hidden, return_first_logits, return_logprobs, prefill_chunk, _Shed(*plan) if plan is not None else None, cons)
+        return self._call(kv_cache_dtype, weight_dtype, req.shed, self._generate, embeds, req, decode_streams)
 
-    def _call_shedding(self, plan, kv_cache_dtype, weight_dtype, fn, *a, **k):
-        """_call for a shedding call (plan = check_shed's (ladder, steps between looks)): fn gets the call's _Shed, and last_plan is stamped with
-        what it recorded.  A retry after an eviction (_retry_after_eviction) starts the record again."""
-        shed = _Shed(*plan)
-
-        def run(*a_, **k_):
-            shed.log, shed.captures = [], 0
-            return fn(*a_, shed=shed, **k_)
-
-        res = self._call(kv_cache_dtype, weight_dtype, run, *a, **k)
-        if isinstance(self.last_plan, dict):
-            self.last_plan["shed"], self.last_plan["shed_captures"] = list(shed.log), shed.captures
-        return res
-
-    def _run_steps(self, sts: List["_DecodeState"], max_new_tokens: int, graphed: bool, side_streams: bool, retire: bool, on_step=None,
-                   sampled_step=None, shed: Optional["_Shed"] = None):
+    def _run_steps(self, sts: List["_DecodeState"], req: _Request, side_streams: bool, retire: bool, on_step=None, sampled_step=None):
         """The decode steps 1 .. max_new_tokens - 1 of started states (step 0, the first token, is _start's): THE step loop of the engine.
-        graphed: every state's step is captured under its own scratch slot (or its graph reused, _capture) and replayed; else the step runs
+        req.graphed: every state's step is captured under its own scratch slot (or its graph reused, _capture) and replayed; else the step runs
         eagerly.  side_streams: every state steps on a HIP stream of its own, forked from the current stream before the first step and joined
         to it after the last; else all steps go to the current stream.  The loop holds no host synchronisation but the EOS check: every
         EOS_CHECK_EVERY steps (a lookup state: every step) the `finished` flags are read, and
@@ -1602,9 +1676,10 @@ class GenerationEngine:
                           their buffers are joined column by column).
         on_step(sts[0]) runs after every step.  sampled_step(step, sts[0]) is asked before every graphed step of the FIRST state and returns
         True when it has run that step itself (bench.py's roofline sampling); the state is device-resident, so replays continue after it.
-        shed (shed_finished; ONE state on the current stream): the EOS check reads the `finished` vector instead of its .all() - still the
+        req.shed (shed_finished; ONE state on the current stream): the EOS check reads the `finished` vector instead of its .all() - still the
         loop's only synchronisation, every shed.every steps - and when the unfinished rows fit a smaller rung of the ladder, sts[0] is
         replaced IN THE LIST by the child state that carries them on (_shed_to).  The ids of the whole wave are then in shed.out."""
+        max_new_tokens, graphed, shed = req.max_new_tokens, req.graphed, req.shed
         main = torch.cuda.current_stream()
         graphs, streams = [], []
         if shed is not None:
@@ -1667,11 +1742,7 @@ class GenerationEngine:
             for sg in streams:
                 main.wait_stream(sg)
 
-    def _generate(self, embeds: torch.Tensor, max_new_tokens: int, eos_token_id: Optional[int] = None,
-                  pad_token_id: Optional[int] = None, min_new_tokens: int = 0, prefill_chunk: int = 0, use_graph: bool = True,
-                  return_step_logits: bool = False, return_hidden: bool = False, decode_streams: int = 1,
-                  return_first_logits: bool = False, sampling=None, constraint=None, return_logprobs: bool = False, processors=None,
-                  shed: Optional["_Shed"] = None):
+    def _generate(self, embeds: torch.Tensor, req: _Request, decode_streams: int = 1):
         """Greedy generation from inputs_embeds only, as UnifiedForCausalLM.generate drives HF generate
         (unified_llama.py:262-267): positions 0..S-1 (left pads attended), returns ONLY new ids.
 
@@ -1687,28 +1758,12 @@ class GenerationEngine:
         separate HIP streams: the HBM-bound KV-cache attention of one group overlaps the MFMA-bound projections of
         another.  Rows never interact, so the split only changes which M the projection kernels see."""
         B, S, D = embeds.shape
-        groups = self.plan_batch(B, S, max_new_tokens, slots=max(1, decode_streams))
+        groups = self.plan_batch(B, S, req.max_new_tokens, slots=max(1, decode_streams))
         if len(groups) > 1:
-            return self._generate_split(groups, embeds, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, prefill_chunk, use_graph,
-                                        return_step_logits, return_hidden, return_first_logits, sampling, constraint, return_logprobs,
-                                        processors=processors, shed=shed)
-        graphed = use_graph and max_new_tokens > 2
-        G = decode_streams if (decode_streams > 1 and graphed and B >= decode_streams and
-                               not return_step_logits and not return_hidden) else 1
-        step_logits, hiddens, first_logits = [], [], []
-
-        def sink(st):
-            if return_first_logits and len(first_logits) < G:
-                first_logits.append(st.logits.clone())
-            if return_step_logits and st.rows is not None:
-                # a child state of a wave that shed rows: its real rows under their indices in the whole wave, zeros where a row has left
-                full = torch.zeros((B,) + tuple(st.logits.shape[1:]), device=st.logits.device, dtype=st.logits.dtype)
-                full[st.rows_idx] = st.logits[:st.n_real]
-                step_logits.append(full)
-            elif return_step_logits:
-                step_logits.append(st.logits.clone())
-            if return_hidden:
-                hiddens.append(st.hn.clone())
+            return self._generate_split(groups, embeds, req)
+        G = decode_streams if (decode_streams > 1 and req.graphed and B >= decode_streams and
+                               not req.return_step_logits and not req.return_hidden) else 1
+        sink = _Collect(req, G, B)
 
         def sampled_step(step, st):
             # roofline sampling (bench.py): this step runs the same launches eagerly with HIP events around the decode-attention kernel
@@ -1724,33 +1779,20 @@ class GenerationEngine:
         sts = []
         for g in range(G):
             with _ws_slot(g):
-                sts.append(self._start(embeds[B * g // G:B * (g + 1) // G], max_new_tokens, eos_token_id, pad_token_id, min_new_tokens,
-                                       prefill_chunk, return_hidden, g, sink, sampling,
-                                       constraint.rows(B * g // G, B * (g + 1) // G) if constraint is not None else None, return_logprobs,
-                                       processors=processors))
+                b0, b1 = B * g // G, B * (g + 1) // G
+                sts.append(self._start(embeds[b0:b1], req.rows(b0, b1), g, sink))
         if ops.PROFILER is not None:
             ops.PROFILER.mark("prefill_end")
         # the groups are ONE call: all of them step until all have finished (a retired group's buffer would hold the fill value, not its pad id)
-        self._run_steps(sts, max_new_tokens, graphed, G > 1, False, sink, sampled_step, shed=shed)
+        self._run_steps(sts, req, G > 1, False, sink, sampled_step)
         if ops.PROFILER is not None:
             ops.PROFILER.mark("decode_end")
         n_done = int(sts[0].step_dev.item())
-        if shed is not None and shed.out is not None:         # the wave shed rows: its ids were assembled under the rows' original indices
-            out = _trim_at_eos(shed.out, n_done, sts[0].eos_all)
+        if req.shed is not None and req.shed.out is not None:         # the wave shed rows: its ids were assembled under the rows' original indices
+            ids = req.shed.out
         else:
-            out = _trim_at_eos(sts[0].out_ids if G == 1 else torch.cat([st.out_ids for st in sts], 0), n_done, sts[0].eos_all)
-        # st.out_ids is the persistent, graph-baked buffer the next generate() refills: hand the caller its own tensor (HF
-        # generate returns fresh tensors; a caller that collects results over batches must not see them overwritten)
-        res = [out.clone()]
-        if return_step_logits:
-            res.append(torch.stack(step_logits, 1)[:, : out.shape[1]])
-        if return_hidden:
-            res.append(torch.stack(hiddens, 1)[:, : out.shape[1]])
-        if return_first_logits:
-            res.append(first_logits[0] if G == 1 else torch.cat(first_logits, 0))
-        if return_logprobs:
-            res.append(torch.cat([_lp_rows(st, 0, st.B, out.shape[1]) for st in sts], 0))
-        return res[0] if len(res) == 1 else tuple(res)
+            ids = sts[0].out_ids if G == 1 else torch.cat([st.out_ids for st in sts], 0)
+        return sink.whole(sts, _trim_at_eos(ids, n_done, sts[0].eos_all))
 
     @torch.no_grad()
     def generate_many(self, embeds_list: List[torch.Tensor], max_new_tokens: int, eos_token_id: Optional[int] = None,
@@ -1776,19 +1818,12 @@ class GenerationEngine:
             raise NotImplementedError("shed_finished with coalesce=False: the batches in flight are states of their own that retire as a whole "
                                       "(use coalesce=True, or generate() per batch)")
         cons = self._constraints(constraint, [int(e.shape[0]) for e in embeds_list], eos_token_id, min_new_tokens) if constraint is not None else None
-        if plan is not None:
-            return self._call_shedding(plan, kv_cache_dtype, weight_dtype, self._generate_many, embeds_list, max_new_tokens, eos_token_id,
-                                       pad_token_id, min_new_tokens, use_graph, sampling, return_first_logits, coalesce, max_rows,
-                                       return_step_logits, return_hidden, cons, return_logprobs, processors=proc)
-        return self._call(kv_cache_dtype, weight_dtype, self._generate_many, embeds_list, max_new_tokens, eos_token_id, pad_token_id,
-                          min_new_tokens, use_graph, sampling, return_first_logits, coalesce, max_rows, return_step_logits, return_hidden, cons,
-                          return_logprobs, processors=proc)
+        req = _Request(max_new_tokens, one_eos(eos_token_id, ONE_EOS), pad_token_id, min_new_tokens, use_graph, sampling, proc, return_step_logits,
+                       return_hidden, return_first_logits, return_logprobs, shed=_Shed(*plan) if plan is not None else None)
+        return self._call(kv_cache_dtype, weight_dtype, req.shed, self._generate_many, embeds_list, req, cons, coalesce, max_rows)
 
-    def _generate_many(self, embeds_list: List[torch.Tensor], max_new_tokens: int, eos_token_id: Optional[int] = None,
-                       pad_token_id: Optional[int] = None, min_new_tokens: int = 0, use_graph: bool = True, sampling=None,
-                       return_first_logits: bool = False, coalesce: bool = False, max_rows: Optional[int] = None,
-                       return_step_logits: bool = False, return_hidden: bool = False, constraints=None, return_logprobs: bool = False,
-                       processors=None, shed=None):
+    def _generate_many(self, embeds_list: List[torch.Tensor], req: _Request, constraints=None, coalesce: bool = False,
+                       max_rows: Optional[int] = None):
         """Several INDEPENDENT batches in flight: each element of `embeds_list` ([B_i, S_i, D], its own prompt length and left padding, i.e.
         exactly what one generate() call of the reference's eval loop gets) becomes one decode group with its own KV cache, decode state
         and captured HIP graph; the groups are prefilled one after the other and their decode steps are replayed on separate HIP streams.
@@ -1813,114 +1848,66 @@ class GenerationEngine:
             return []
         G = len(embeds_list)
         cons = constraints if constraints is not None else [None] * G      # one _Constraint per batch
-        if (return_step_logits or return_hidden) and (not coalesce or return_first_logits or (return_step_logits and return_hidden)):
+        per_step = req.return_step_logits or req.return_hidden
+        if per_step and (not coalesce or req.return_first_logits or (req.return_step_logits and req.return_hidden)):
             raise NotImplementedError("generate_many: return_step_logits / return_hidden are options of the coalesced form, one at a time (use generate() per batch otherwise)")
-        if coalesce and (G > 1 or return_step_logits or return_hidden):
-            return self._generate_coalesced(embeds_list, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling,
-                                            return_first_logits, max_rows, return_step_logits, return_hidden, cons, return_logprobs,
-                                            processors=processors, shed=shed)
+        if coalesce and (G > 1 or per_step):
+            return self._generate_coalesced(embeds_list, req, cons, max_rows)
         if G == 1:
-            return [self._generate(embeds_list[0], max_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id, min_new_tokens=min_new_tokens,
-                                   use_graph=use_graph, sampling=sampling, return_first_logits=return_first_logits, constraint=cons[0],
-                                   return_logprobs=return_logprobs, processors=processors, shed=shed)]
+            return [self._generate(embeds_list[0], req.replace(constraint=cons[0]))]
+        max_new_tokens = req.max_new_tokens
         need = sum(e.shape[0] * self.bytes_per_sequence(e.shape[1], max_new_tokens) for e in embeds_list) + self.fixed_bytes(max(e.shape[0] for e in embeds_list),
                                                                                                                             max(e.shape[1] for e in embeds_list))
         budget = self.memory_budget(0, 0, slots=G)
         if need > 0.94 * budget:
             raise MemoryError(f"generate_many: {G} batches need {need / 2**30:.1f} GiB of KV cache and scratch, {budget / 2**30:.1f} GiB available: put fewer in flight")
-        firsts = []
-
-        def sink(st):
-            if return_first_logits:
-                firsts.append(st.logits.clone())
-
         self._rope_tab(max(_round_up(e.shape[1] + max_new_tokens, 64) for e in embeds_list))    # grown ONCE: every group's launches bake its pointer
-        sts = []
+        sts, sinks = [], [_Collect(req) for _ in embeds_list]      # every batch is a call of its own: its own first logits
         for g, emb in enumerate(embeds_list):
             with _ws_slot(g):
-                sts.append(self._start(emb, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, 0, False, g, sink, sampling, cons[g],
-                                       return_logprobs, processors=processors))
-        self._run_steps(sts, max_new_tokens, use_graph and max_new_tokens > 2, True, True)
-        outs = []
-        for g, st in enumerate(sts):
-            out = _trim_at_eos(st.out_ids, int(st.step_dev.item()), st.eos_all).clone()
-            r = (out, firsts[g]) if return_first_logits else (out,)
-            if return_logprobs:
-                r += (_lp_rows(st, 0, st.B, out.shape[1]),)
-            outs.append(r if len(r) > 1 else out)
-        return outs
+                sts.append(self._start(emb, req.replace(constraint=cons[g]), g, sinks[g]))
+        self._run_steps(sts, req, True, True)
+        return [sinks[g].rows(st, st.out_ids, 0, st.B, int(st.step_dev.item())) for g, st in enumerate(sts)]
 
-    def _generate_coalesced(self, embeds_list, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling,
-                            return_first_logits, max_rows, return_step_logits=False, return_hidden=False, cons=None, return_logprobs=False,
-                            processors=None, shed=None):
+    def _generate_coalesced(self, embeds_list, req: _Request, cons, max_rows):
         """generate_many(coalesce=True): pack the batches, in order, into waves of at most `cap` rows (the weight-streaming regime of the decode
         projections, and what the device's memory holds at the longest prompt), run every wave as one ragged batch."""
         Bs = [int(e.shape[0]) for e in embeds_list]
         Smax = max(int(e.shape[1]) for e in embeds_list)
         cap = min(int(max_rows), ops.DECODE_MAX_ROWS) if max_rows else ops.DECODE_MAX_ROWS
-        per = self.bytes_per_sequence(Smax, max_new_tokens)
+        per = self.bytes_per_sequence(Smax, req.max_new_tokens)
         budget = self.memory_budget(0, 0, slots=1)
         fit = (int(0.94 * budget) - self.fixed_bytes(min(sum(Bs), cap), Smax)) // per
         waves = _pack_waves(Bs, max(1, min(cap, fit)))
         plan = {"B": sum(Bs), "groups": [sum(Bs[g] for g in w) for w in waves], "bytes_per_seq": per, "budget": budget, "coalesced": True}
         outs = [None] * len(embeds_list)
-        cons = cons if cons is not None else [None] * len(embeds_list)
         for w in waves:
             if len(w) == 1:                                    # a lone batch (or one larger than the cap: _generate plans its own split)
-                g = w[0]
-                outs[g] = self._generate(embeds_list[g], max_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
-                                         min_new_tokens=min_new_tokens, use_graph=use_graph, sampling=sampling, return_first_logits=return_first_logits,
-                                         return_step_logits=return_step_logits, return_hidden=return_hidden, constraint=cons[g],
-                                         return_logprobs=return_logprobs, processors=processors, shed=shed)
+                outs[w[0]] = self._generate(embeds_list[w[0]], req.replace(constraint=cons[w[0]]))
                 continue
             # the rows of the wave are the rows of its batches in wave order: so are their trie roots
             wc = _Constraint(cons[w[0]].dev, [r for g in w for r in cons[g].roots]) if cons[w[0]] is not None else None
-            res = self._ragged_wave([embeds_list[g] for g in w], max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling,
-                                    return_first_logits, return_step_logits, return_hidden, wc, return_logprobs, processors=processors, shed=shed)
+            res = self._ragged_wave([embeds_list[g] for g in w], req.replace(constraint=wc))
             for g, r in zip(w, res):
                 outs[g] = r
         self.last_plan = plan
         return outs
 
-    def _ragged_wave(self, embeds_list, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling, return_first_logits,
-                     return_step_logits=False, return_hidden=False, constraint=None, return_logprobs=False, processors=None, shed=None):
-        firsts, steps = [], []
-
-        def sink(st):
-            if return_first_logits and not firsts:
-                firsts.append(st.logits.clone())
-            if return_step_logits:
-                steps.append(st.logits.clone())
-            if return_hidden:
-                steps.append(st.hn.clone())
-
+    def _ragged_wave(self, embeds_list, req: _Request):
+        sink = _Collect(req)
         with _ws_slot(0):
-            st = self._start_ragged(embeds_list, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, sink, sampling, return_hidden, constraint,
-                                    return_logprobs, processors=processors)
+            st = self._start_ragged(embeds_list, req, sink)
         if ops.PROFILER is not None:
             ops.PROFILER.mark("prefill_end")
         sts = [st]
-        self._run_steps(sts, max_new_tokens, use_graph and max_new_tokens > 2, False, True,
-                        sink if (return_step_logits or return_hidden) else None, shed=shed)
+        self._run_steps(sts, req, False, True, sink.on_step)
         if ops.PROFILER is not None:
             ops.PROFILER.mark("decode_end")
         n_done = int(sts[0].step_dev.item())                   # a wave that shed rows ends in a child state: the counters went with it
+        shed = req.shed
         ids = shed.out if (shed is not None and shed.out is not None) else st.out_ids      # ... and its ids were assembled in shed.out
-        sl = torch.stack(steps, 1) if (return_step_logits or return_hidden) else None
-        outs, r0 = [], 0
-        for e in embeds_list:
-            r1 = r0 + int(e.shape[0])
-            # what this batch's own generate() call returns: HF stops a call as soon as all of ITS rows have finished
-            out = _trim_at_eos(ids[r0:r1], n_done, st.eos_all).clone()
-            if return_step_logits or return_hidden:
-                r = (out, sl[r0:r1, : out.shape[1]].clone())
-            else:
-                r = (out, firsts[0][r0:r1].clone()) if return_first_logits else (out,)
-            if return_logprobs:
-                r += (_lp_rows(st, r0, r1, out.shape[1]),)
-            outs.append(r if len(r) > 1 else out)
-            r0 = r1
-        return outs
+        # every batch gets what its own generate() call returns: HF stops a call as soon as all of ITS rows have finished
+        return sink.groups(st, ids, [int(e.shape[0]) for e in embeds_list], n_done)
 
     # ------------------------------------------------------------------ classifier-free guidance: a clip's two prompts as two rows of one wave
     @torch.no_grad()
@@ -1964,73 +1951,52 @@ class GenerationEngine:
                              f"{tuple(negative_embeds.shape)}")
         if embeds.shape[0] != negative_embeds.shape[0] or embeds.shape[0] < 1:
             raise ValueError(f"generate_guided: {embeds.shape[0]} prompts and {negative_embeds.shape[0]} negative prompts - one negative prompt per row")
-        if isinstance(eos_token_id, (list, tuple)):
-            if len(set(int(e) for e in eos_token_id)) > 1:
-                raise NotImplementedError(f"eos_token_id = {list(eos_token_id)}: a guided call stops on ONE id")
-            eos_token_id = eos_token_id[0] if len(eos_token_id) else None
+        eos = one_eos(eos_token_id, "a guided call stops on ONE id")
         if int(max_new_tokens) < 1:
             raise ValueError(f"`max_new_tokens` must be greater than 0, but is {max_new_tokens}.")
         cap = (min(int(max_rows), ops.DECODE_MAX_ROWS) if max_rows else ops.DECODE_MAX_ROWS) // 2
         if cap < 1:
             raise ValueError(f"max_rows = {max_rows}: a pair needs two rows")
-        sampling = normalize_sampling(sampling)
-        return self._call(kv_cache_dtype, weight_dtype, self._generate_guided, embeds, negative_embeds, g, int(max_new_tokens), eos_token_id,
-                          pad_token_id, int(min_new_tokens), use_graph, sampling, return_step_logits, cap)
+        req = _Request(int(max_new_tokens), eos, pad_token_id, int(min_new_tokens), use_graph, normalize_sampling(sampling),
+                       return_step_logits=return_step_logits)
+        return self._call(kv_cache_dtype, weight_dtype, None, self._generate_guided, embeds, negative_embeds, g, cap, req)
 
-    def _generate_guided(self, embeds, negative_embeds, scale, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling,
-                         return_step_logits, cap):
+    def _generate_guided(self, embeds, negative_embeds, scale, cap, req: _Request):
         """Plan the waves - whole pairs, at most `cap` per wave and what the device's memory holds - run them, join them as _generate_split
-        joins the groups of a split batch (a wave that stopped early is padded with pad ids / zero logits)."""
+        joins the groups of a split batch (_join: a wave that stopped early is padded with pad ids / zero logits)."""
         embeds = embeds.to(device=self.device, dtype=BF16)
         negative_embeds = negative_embeds.to(device=self.device, dtype=BF16)
         B = int(embeds.shape[0])
         Smax = max(int(embeds.shape[1]), int(negative_embeds.shape[1]))
-        per = 2 * self.bytes_per_sequence(Smax, max_new_tokens) + self.lm_head.weight.shape[0] * 4       # both rows sit in one cache of Smax rows; + the guided row
+        per = 2 * self.bytes_per_sequence(Smax, req.max_new_tokens) + self.lm_head.weight.shape[0] * 4       # both rows sit in one cache of Smax rows; + the guided row
         budget = self.memory_budget(0, 0, slots=1)
         fit = (int(0.94 * budget) - self.fixed_bytes(2 * min(B, cap), Smax)) // per
         n_waves = -(-B // max(1, min(cap, fit)))
         sizes = [B // n_waves + (1 if i < B % n_waves else 0) for i in range(n_waves)]
         plan = {"B": B, "groups": sizes, "bytes_per_seq": per, "budget": budget, "guided": True}
-        pad = int(pad_token_id) if pad_token_id is not None else (int(eos_token_id) if eos_token_id is not None else 0)
-        ids, cond, unc, b0 = [], [], [], 0
+        parts, b0 = [], 0
         for n in sizes:
-            smp = reseed_sampling(sampling, 104729 * b0)
-            out, sl = self._guided_wave(embeds[b0:b0 + n], negative_embeds[b0:b0 + n], scale, max_new_tokens, eos_token_id, pad_token_id,
-                                        min_new_tokens, use_graph, smp, return_step_logits)
-            ids.append(out)
-            if return_step_logits:
-                cond.append(sl[:n]); unc.append(sl[n:])
+            parts.append(self._guided_wave(embeds[b0:b0 + n], negative_embeds[b0:b0 + n],
+                                           req.replace(sampling=reseed_sampling(req.sampling, 104729 * b0), cfg=(scale, n))))
             b0 += n
         self.last_plan = plan
-        n_max = max(t.shape[1] for t in ids)
+        res = _join(parts, req.join_pad)
+        # the raw step logits of the whole call: every wave's conditional rows, then every wave's unconditional rows
+        return (res[0], torch.cat(res[1:], 0)) if req.return_step_logits else res[0]
 
-        def widen(t, fill):
-            if t.shape[1] == n_max:
-                return t
-            return torch.cat([t, torch.full((t.shape[0], n_max - t.shape[1]) + tuple(t.shape[2:]), fill, device=t.device, dtype=t.dtype)], 1)
-
-        out = ids[0] if n_waves == 1 else torch.cat([widen(t, pad) for t in ids], 0)
-        if not return_step_logits:
-            return out
-        return out, torch.cat([widen(t, 0) for t in cond + unc], 0)
-
-    def _guided_wave(self, embeds, negative_embeds, scale, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling,
-                     return_step_logits):
-        """One wave of whole pairs: a ragged state of two groups.  Returns fresh (ids of the conditional rows [B, n], raw step logits
-        [2B, n, V] or None)."""
+    def _guided_wave(self, embeds, negative_embeds, req: _Request):
+        """One wave of whole pairs (req.cfg = (scale, pairs)): a ragged state of two groups.  Returns fresh (ids of the conditional rows
+        [B, n],) and, with return_step_logits, the raw step logits [B, n, V] of the conditional and of the unconditional rows."""
         B = int(embeds.shape[0])
-        steps = []
-
-        def sink(st):
-            if return_step_logits:
-                steps.append(st.logits.clone())
-
+        sink = _Collect(req)
         with _ws_slot(0):
-            st = self._start_ragged([embeds, negative_embeds], max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, sink, sampling,
-                                    cfg=(scale, B))
-        self._run_steps([st], max_new_tokens, use_graph and max_new_tokens > 2, False, True, sink if return_step_logits else None)
+            st = self._start_ragged([embeds, negative_embeds], req, sink)
+        self._run_steps([st], req, False, True, sink.on_step)
         out = _trim_at_eos(st.out_ids[:B], int(st.step_dev.item()), st.eos_all).clone()
-        return out, (torch.stack(steps, 1)[:, : out.shape[1]] if return_step_logits else None)
+        if not req.return_step_logits:
+            return (out,)
+        sl = torch.stack(sink.steps, 1)[:, : out.shape[1]]
+        return out, sl[:B], sl[B:]
 
     # ------------------------------------------------------------------ several questions per clip on one prefix KV
     def shared_prefix_bytes(self, C: int, P: int, B: int, S: int, max_new_tokens: int) -> int:
@@ -2121,17 +2087,16 @@ class GenerationEngine:
         sampling = normalize_sampling(sampling, constraint is not None)
         proc = check_processors(processors, min_new_tokens, constraint is not None, return_logprobs, eos_token_id)
         cons = self._constraints(constraint, [len(qs) for qs in suffix_embeds], eos_token_id, min_new_tokens) if constraint is not None else None
-        return self._call(kv_cache_dtype, weight_dtype, self._generate_shared_prefix, prefix_embeds, suffix_embeds, max_new_tokens, eos_token_id,
-                          pad_token_id, min_new_tokens, use_graph, sampling, return_first_logits, return_step_logits, max_rows, cons, return_logprobs,
-                          processors=proc)
+        req = _Request(max_new_tokens, one_eos(eos_token_id, ONE_EOS), pad_token_id, min_new_tokens, use_graph, sampling, proc,
+                       return_step_logits=return_step_logits, return_first_logits=return_first_logits, return_logprobs=return_logprobs)
+        return self._call(kv_cache_dtype, weight_dtype, None, self._generate_shared_prefix, prefix_embeds, suffix_embeds, req, cons, max_rows)
 
-    def _generate_shared_prefix(self, prefix_embeds, suffix_embeds, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling,
-                                return_first_logits, return_step_logits, max_rows, cons=None, return_logprobs=False, processors=None):
+    def _generate_shared_prefix(self, prefix_embeds, suffix_embeds, req: _Request, cons, max_rows):
         if self._fp8:
             raise NotImplementedError('kv_cache_dtype="fp8_e4m3" with a shared prefix (generate_shared_prefix) is not implemented: the prefix cache and its attention kernels are bf16')
         if getattr(self, "_w_mode", "bf16") == "fp8_e4m3":
             raise NotImplementedError('weight_dtype="fp8_e4m3" with a shared prefix (generate_shared_prefix) is not implemented')
-        if return_first_logits and return_step_logits:
+        if req.return_first_logits and req.return_step_logits:
             raise NotImplementedError("generate_shared_prefix: return_first_logits / return_step_logits one at a time")
         if prefix_embeds.dim() != 3 or prefix_embeds.dtype != BF16 or prefix_embeds.shape[1] < 1:
             raise ValueError("prefix_embeds must be a bf16 [C, P, D] tensor with P >= 1")
@@ -2142,42 +2107,40 @@ class GenerationEngine:
         Gs = [len(qs) for qs in suffix_embeds]
         Smax = max(int(q.shape[0]) for qs in suffix_embeds for q in qs)
         outs = []
-        for w in self.plan_shared_prefix(Gs, P, Smax, max_new_tokens, max_rows):
+        for w in self.plan_shared_prefix(Gs, P, Smax, req.max_new_tokens, max_rows):
             wc = _Constraint(cons[w[0]].dev, [r for c in w for r in cons[c].roots]) if cons is not None else None      # one root per question, in row order
-            outs += self._shared_prefix_wave(prefix_embeds[w[0]:w[-1] + 1], [suffix_embeds[c] for c in w], max_new_tokens, eos_token_id, pad_token_id,
-                                             min_new_tokens, use_graph, sampling, return_first_logits, return_step_logits, wc, return_logprobs, processors=processors)
+            outs += self._shared_prefix_wave(prefix_embeds[w[0]:w[-1] + 1], [suffix_embeds[c] for c in w], req.replace(constraint=wc))
         return outs
 
-    def _shared_prefix_wave(self, prefix_embeds, suffix_embeds, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, use_graph, sampling,
-                            return_first_logits, return_step_logits, constraint=None, return_logprobs=False, processors=None):
+    def _prefix_state(self, prefix_embeds, Gs: List[int], lens: List[int], req: _Request):
+        """The set-up of a wave whose rows attend a per-clip prefix (generate_shared_prefix, generate_beam; Gs[c] consecutive rows per clip, row b
+        with lens[b] own prompt rows): RoPE table and prefix buffers (before any launch bakes a pointer: positions run to P + Tmax), the prefix
+        through the existing prefill, once per clip (no lm_head product), then the rows' ragged state - its key extended by the buffers'."""
         C, P, D = prefix_embeds.shape
+        lay = shared_prefix_layout(P, lens, req.max_new_tokens)
+        self._rope_tab(P + lay["Tmax"])
+        px = self._shared_prefix_buffers(C, P, Gs, lay["Smax"])
+        b0 = 0
+        for n in self.plan_prefill_chunks(C, P):
+            self.prefill(prefix_embeds[b0:b0 + n], px.decode.pk, px.decode.pv, b0=b0, want_logits=False)
+            b0 += n
+        st = self._state(len(lens), lay["Smax"], req.replace(extra_key=px.key + req.extra_key), 0, ragged=True)
+        st.prefix = px.decode
+        st.row_off.copy_(torch.tensor(lay["first_slot"], dtype=torch.int32))
+        px.decode.rope_off.copy_(torch.tensor(lay["rope_off"], dtype=torch.int32))
+        return st, px, lay
+
+    def _shared_prefix_wave(self, prefix_embeds, suffix_embeds, req: _Request):
+        D = prefix_embeds.shape[2]
         Gs = [len(qs) for qs in suffix_embeds]
         flat = [q for qs in suffix_embeds for q in qs]
-        lay = shared_prefix_layout(P, [int(q.shape[0]) for q in flat], max_new_tokens)
-        B, Smax, Tmax = len(flat), lay["Smax"], lay["Tmax"]
+        B, Smax = len(flat), max(int(q.shape[0]) for q in flat)
         assert B * Smax <= SUFFIX_PASS_ROWS, "plan_shared_prefix sizes the waves for one suffix prefill pass"
         dev = self.device
-        self._rope_tab(P + Tmax)                               # grown before any launch bakes its pointer: positions run to P + Tmax
-        px = self._shared_prefix_buffers(C, P, Gs, Smax)
-        firsts, steps = [], []
-
-        def sink(st):
-            if return_first_logits and not firsts:
-                firsts.append(st.logits.clone())
-            if return_step_logits:
-                steps.append(st.logits.clone())
-
+        sink = _Collect(req)
         with _ws_slot(0):
-            # ---- the prefix: the existing prefill, once per clip (its last-row logits are not needed: no lm_head product)
-            b0 = 0
-            for n in self.plan_prefill_chunks(C, P):
-                self.prefill(prefix_embeds[b0:b0 + n], px.decode.pk, px.decode.pv, b0=b0, want_logits=False)
-                b0 += n
-            st = self._state(B, Smax, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, False, 0, sampling, ragged=True, extra_key=px.key,
-                             constraint=constraint, logprobs=return_logprobs, processors=processors)
-            st.prefix = px.decode
-            st.row_off.copy_(torch.tensor(lay["first_slot"], dtype=torch.int32))
-            px.decode.rope_off.copy_(torch.tensor(lay["rope_off"], dtype=torch.int32))
+            st, px, lay = self._prefix_state(prefix_embeds, Gs, [int(q.shape[0]) for q in flat], req)
+            Tmax = lay["Tmax"]
             # ---- the questions: one front-padded pass of Smax rows per question over [prefix of the clip ; own keys up to the row's]
             emb = torch.zeros((B, Smax, D), device=dev, dtype=BF16)
             for b, q in enumerate(flat):
@@ -2194,22 +2157,8 @@ class GenerationEngine:
             ops.gemm(st.hn, self.lm_head.weight, out=st.logits, out_fp32=True)
             del emb
             self._first_token(st, sink)
-        self._run_steps([st], max_new_tokens, use_graph and max_new_tokens > 2, False, True, sink if return_step_logits else None)
-        n_done = int(st.step_dev.item())
-        sl = torch.stack(steps, 1) if return_step_logits else None
-        outs, r0 = [], 0
-        for G in Gs:
-            r1 = r0 + G
-            out = _trim_at_eos(st.out_ids[r0:r1], n_done, st.eos_all).clone()
-            if return_step_logits:
-                r = (out, sl[r0:r1, : out.shape[1]].clone())
-            else:
-                r = (out, firsts[0][r0:r1].clone()) if return_first_logits else (out,)
-            if return_logprobs:
-                r += (_lp_rows(st, r0, r1, out.shape[1]),)
-            outs.append(r if len(r) > 1 else out)
-            r0 = r1
-        return outs
+        self._run_steps([st], req, False, True, sink.on_step)
+        return sink.groups(st, st.out_ids, Gs, int(st.step_dev.item()))
 
     # ------------------------------------------------------------------ prompt-lookup speculative decoding: k draft tokens verified per step
     @torch.no_grad()
@@ -2244,23 +2193,23 @@ class GenerationEngine:
             prompt_ids = torch.as_tensor(prompt_ids).reshape(-1)
             if prompt_ids.numel() != S or prompt_ids.dtype.is_floating_point or prompt_ids.dtype == torch.bool:
                 raise ValueError(f"prompt_ids must hold one integer id per prompt row ({S}; -1 = no text token), got {tuple(prompt_ids.shape)} {prompt_ids.dtype}")
-        return self._call(kv_cache_dtype, weight_dtype, self._generate_lookup, embeds, max_new_tokens, k, n, prompt_ids, eos_token_id, pad_token_id,
-                          min_new_tokens, use_graph, return_first_logits, return_step_logits, return_stats)
+        req = _Request(max_new_tokens, one_eos(eos_token_id, ONE_EOS), pad_token_id, min_new_tokens, use_graph, return_step_logits=return_step_logits,
+                       return_first_logits=return_first_logits, lookup=(k, n, bool(return_step_logits)))
+        return self._call(kv_cache_dtype, weight_dtype, None, self._generate_lookup, embeds, prompt_ids, req, return_stats)
 
-    def _generate_lookup(self, embeds, max_new_tokens, k, max_ngram, prompt_ids, eos_token_id, pad_token_id, min_new_tokens, use_graph,
-                         return_first_logits, return_step_logits, return_stats):
+    def _generate_lookup(self, embeds, prompt_ids, req: _Request, return_stats):
         S = int(embeds.shape[1])
+        max_new_tokens, (k, max_ngram, _keep) = req.max_new_tokens, req.lookup
         firsts = []
 
         def sink(st):                                          # the first token's logits: row 0 of the kept rows, and the caller's copy
-            if return_first_logits:
+            if req.return_first_logits:
                 firsts.append(st.logits.clone())
             if st.lookup.step_logits is not None:
                 st.lookup.step_logits[:1].copy_(st.logits)
 
         with _ws_slot(0):
-            st = self._start(embeds, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, 0, False, 0, sink,
-                             lookup=(k, max_ngram, bool(return_step_logits)))
+            st = self._start(embeds, req, 0, sink)
             lk = st.lookup
             if prompt_ids is not None:
                 lk.hist[:S].copy_(prompt_ids.to(torch.int32))
@@ -2269,13 +2218,13 @@ class GenerationEngine:
                 st.finished.fill_(1)
         self.last_plan = {"B": 1, "groups": [1], "mode": "lookup", "num_draft_tokens": k, "max_ngram": max_ngram, "Tmax": st.Tmax}
         # every verify step emits at least one token: max_new_tokens - 1 steps always suffice; _run_steps reads `finished` after every step of a lookup state
-        self._run_steps([st], max_new_tokens, use_graph and max_new_tokens > 2, False, True)
+        self._run_steps([st], req, False, True)
         n_done = int(st.step_dev.item())
         out = _trim_at_eos(st.out_ids, n_done, st.eos_all).clone()
         res = [out]
-        if return_step_logits:
+        if req.return_step_logits:
             res.append(lk.step_logits[None, : out.shape[1]].clone())
-        if return_first_logits:
+        if req.return_first_logits:
             res.append(firsts[0])
         if return_stats:
             s = lk.stats.tolist()
@@ -2321,10 +2270,7 @@ class GenerationEngine:
             raise ValueError(f"`num_return_sequences` ({num_return_sequences}) has to be between 1 and `num_beams` ({K})")
         if embeds.dim() != 3 or embeds.shape[1] < 2:
             raise ValueError(f"generate_beam: embeds must be [B, S, D] with S >= 2 (the prefix needs one row), got {tuple(embeds.shape)}")
-        if isinstance(eos_token_id, (list, tuple)):
-            if len(set(int(e) for e in eos_token_id)) > 1:
-                raise NotImplementedError(f"eos_token_id = {list(eos_token_id)}: beam search stops on ONE id")
-            eos_token_id = eos_token_id[0] if len(eos_token_id) else None
+        eos = one_eos(eos_token_id, "beam search stops on ONE id")
         if int(max_new_tokens) < 1:
             raise ValueError(f"`max_new_tokens` must be greater than 0, but is {max_new_tokens}.")
         if int(max_new_tokens) > ops.BEAM_MAX_NEW:
@@ -2337,47 +2283,38 @@ class GenerationEngine:
             raise NotImplementedError('kv_cache_dtype="fp8_e4m3" with beam search (generate_beam) is not implemented: the prefix cache and its attention kernels are bf16')
         if getattr(self, "_w_mode", "bf16") == "fp8_e4m3":
             raise NotImplementedError('weight_dtype="fp8_e4m3" with beam search (generate_beam) is not implemented')
-        return self._call(None, None, self._generate_beam, embeds, K, int(max_new_tokens), eos_token_id, pad_token_id, int(min_new_tokens),
-                          float(length_penalty), early_stopping, R, use_graph, max_rows, return_scores, trace)
+        lp = float(length_penalty)
+        req = _Request(int(max_new_tokens), eos, pad_token_id, int(min_new_tokens), use_graph, extra_key=("beam", K, lp, early_stopping))
+        ids, scores = self._call(None, None, None, self._generate_beam, embeds, (K, R, lp, early_stopping), req, max_rows, trace)
+        return (ids, scores) if return_scores else ids
 
-    def _generate_beam(self, embeds, K, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, length_penalty, early_stopping, R, use_graph,
-                       max_rows, return_scores, trace):
+    def _generate_beam(self, embeds, beam, req: _Request, max_rows, trace):
+        """beam = (K, returned hypotheses per clip, length_penalty, early_stopping).  Returns (ids, sequences_scores)."""
         embeds = embeds.to(device=self.device, dtype=BF16)
         B, S, D = embeds.shape
+        K, R = beam[:2]
         seqs, scores, lens = [], [], []
-        for w in self.plan_shared_prefix([K] * B, S - 1, 1, max_new_tokens, max_rows):
-            hs, sc, ln = self._beam_wave(embeds[w[0]:w[-1] + 1], K, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, length_penalty,
-                                         early_stopping, use_graph, trace)
+        for w in self.plan_shared_prefix([K] * B, S - 1, 1, req.max_new_tokens, max_rows):
+            hs, sc, ln = self._beam_wave(embeds[w[0]:w[-1] + 1], beam, req, trace)
             seqs.append(hs[:, :R]); scores.append(sc[:, :R]); lens.append(ln[:, :R])
         seqs, scores, lens = torch.cat(seqs, 0), torch.cat(scores, 0), torch.cat(lens, 0)
         n = max(1, int(lens.max().item()))
-        ids = seqs[:, :, :n].reshape(B * R, n).contiguous()
-        return (ids, scores.reshape(B * R).contiguous()) if return_scores else ids
+        return seqs[:, :, :n].reshape(B * R, n).contiguous(), scores.reshape(B * R).contiguous()
 
-    def _beam_wave(self, embeds, K, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, length_penalty, early_stopping, use_graph, trace):
+    def _beam_wave(self, embeds, beam, req: _Request, trace):
         """One wave of whole clips: prefix = all but the last prompt row, once per clip; the K beams of a clip are K copies of the last row.
         Returns fresh (hyp_seq [C, K, max_new], hyp_score [C, K], hyp_len [C, K])."""
         C, S, D = embeds.shape
-        P, rows = S - 1, C * K
-        lay = shared_prefix_layout(P, [1] * rows, max_new_tokens)
-        Tmax = lay["Tmax"]
-        self._rope_tab(P + Tmax)
-        px = self._shared_prefix_buffers(C, P, [K] * C, 1)
+        K, _R, length_penalty, early_stopping = beam
+        P, rows, max_new_tokens = S - 1, C * K, req.max_new_tokens
         with _ws_slot(0):
-            b0 = 0
-            for n in self.plan_prefill_chunks(C, P):
-                self.prefill(embeds[b0:b0 + n, :P], px.decode.pk, px.decode.pv, b0=b0, want_logits=False)
-                b0 += n
-            st = self._state(rows, 1, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, False, 0, None, ragged=True,
-                             extra_key=px.key + ("beam", K, float(length_penalty), early_stopping))
+            st, px, lay = self._prefix_state(embeds[:, :P], [K] * C, [1] * rows, req)
+            Tmax = lay["Tmax"]
             if st.beam is None:
                 st.beam = ops.BeamState(C, K, max_new_tokens, st.pad, length_penalty, early_stopping, self.device)
             else:
                 st.beam.reset()
             st.out_ids.fill_(st.pad)                           # the running histories: HF's fill value
-            st.prefix = px.decode
-            st.row_off.copy_(torch.tensor(lay["first_slot"], dtype=torch.int32))
-            px.decode.rope_off.copy_(torch.tensor(lay["rope_off"], dtype=torch.int32))
             ws = self._workspace(rows)
             last = embeds[:, P:].expand(C, K, D).reshape(rows, D).contiguous()
             ops.cast_rows(last, ws.x, rows, D)
@@ -2397,13 +2334,11 @@ class GenerationEngine:
             trace_steps = []
             self._first_token(st)
             sink(st)
-        self._run_steps([st], max_new_tokens, use_graph and max_new_tokens > 2, False, True, sink if trace is not None else None)
+        self._run_steps([st], req, False, True, sink if trace is not None else None)
         bs = st.beam
         return (bs.hyp_seq.view(C, K, max_new_tokens).clone(), bs.hyp_score.view(C, K).clone(), bs.hyp_len.view(C, K).clone())
 
-    def _generate_split(self, groups, embeds, max_new_tokens, eos_token_id, pad_token_id, min_new_tokens, prefill_chunk, use_graph,
-                        return_step_logits, return_hidden, return_first_logits, sampling=None, constraint=None, return_logprobs=False,
-                        processors=None, shed=None):
+    def _generate_split(self, groups, embeds, req: _Request):
         """The batch does not fit the device's memory in one piece: generate the groups one after the other (rows are independent,
         so the results are those of the one-piece run up to the kernel choice a different M implies) and join them.  A group
         that finished early (EOS) is padded to the longest group's length with pad ids, like HF pads finished rows."""
@@ -2411,36 +2346,20 @@ class GenerationEngine:
         p = self.last_plan
         warnings.warn(f"generate(): {p['B']} sequences x {p['bytes_per_seq'] / 2**20:.0f} MiB do not fit the {p['budget'] / 2**30:.1f} GiB "
                       f"available on {self.device}: running {len(groups)} groups of {groups} one after the other", RuntimeWarning)
-        pad = int(pad_token_id) if pad_token_id is not None else (int(eos_token_id) if eos_token_id is not None else 0)
         parts, b0 = [], 0
         saved = self.kv_budget_bytes
         for n in groups:
             self.kv_budget_bytes = 1 << 62                    # the group sizes are decided: no re-planning inside
             try:
-                r = self._generate(embeds[b0:b0 + n], max_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
-                                   min_new_tokens=min_new_tokens, prefill_chunk=prefill_chunk, use_graph=use_graph,
-                                   return_step_logits=return_step_logits, return_hidden=return_hidden, return_first_logits=return_first_logits,
-                                   sampling=reseed_sampling(sampling, 104729 * b0),
-                                   constraint=constraint.rows(b0, b0 + n) if constraint is not None else None, return_logprobs=return_logprobs,
-                                   processors=processors, shed=shed)
+                r = self._generate(embeds[b0:b0 + n], req.rows(b0, b0 + n).replace(sampling=reseed_sampling(req.sampling, 104729 * b0)))
             finally:
                 self.kv_budget_bytes = saved
             parts.append(r if isinstance(r, tuple) else (r,))
             b0 += n
         self.last_plan = p
-        n_max = max(q[0].shape[1] for q in parts)
-        res = []
-        for j in range(len(parts[0])):
-            cols = []
-            for q in parts:
-                t = q[j]
-                per_step = t.dim() >= 2 and not (return_first_logits and j == len(parts[0]) - 1 - int(return_logprobs))      # the scores come last
-                if per_step and t.shape[1] < n_max:
-                    fill = torch.full((t.shape[0], n_max - t.shape[1]) + tuple(t.shape[2:]), pad if j == 0 else 0, device=t.device, dtype=t.dtype)
-                    t = torch.cat([t, fill], 1)
-                cols.append(t)
-            res.append(torch.cat(cols, 0))
-        return res[0] if len(res) == 1 else tuple(res)
+        # the first logits sit behind the per-step tensors, the scores come last (_Collect.whole)
+        res = _join(parts, req.join_pad, keep=len(parts[0]) - 1 - int(req.return_logprobs) if req.return_first_logits else None)
+        return res[0] if len(res) == 1 else res
 
     # ------------------------------------------------------------------ shed_finished: a wave drops its finished rows
     @staticmethod
@@ -2472,32 +2391,17 @@ class GenerationEngine:
         # the one upload of a shed (the live list, before the compaction is launched): every index below is made from it on the device, so
         # nothing here waits for the compaction
         idx = ops.kv_compact_rows(st.kc, st.vc, live, st.pos_dev, st.row_off).to(torch.int64)
-        w8 = self._w8_rows(Bp)
-        w8_key = ("fp8_e4m3",) + tuple(t.data_ptr() for pair in self._quantized() for t in pair) if w8 else ("bf16",)
+        w8, w8_key = self._w8_rows(Bp), self._w8_key(Bp)
         ch = root.children.get((Bp, w8_key))
         if ch is None:
-            V, n_cols = self.lm_head.weight.shape[0], root.out_ids.shape[1]
-            ch = _DecodeState()
-            ch.key, ch.graph = root.key + ("shed", Bp) + w8_key, None
-            ch.B, ch.Tmax, ch.kc, ch.vc, ch.slot = Bp, root.Tmax, root.kc[:, :Bp], root.vc[:, :Bp], root.slot
-            ch.ks = ch.vs = None
-            ch.w8 = w8
+            ch = _DecodeState()                                # a plain greedy / sampling state: check_shed refuses every option that owns more
+            ch.key = _child_key(root.key, Bp, w8_key)
+            ch.B, ch.Tmax, ch.kc, ch.vc, ch.slot, ch.w8 = Bp, root.Tmax, root.kc[:, :Bp], root.vc[:, :Bp], root.slot, w8
             tc, uc = self._ws_cols()
             ch.ws = _Workspace(self.cfg, Bp, dev, tc, uc)
-            ch.lookup = None
-            ch.logits = torch.empty((Bp, V), device=dev, dtype=torch.float32)
-            ch.hn = None                                       # return_hidden is refused with the option: no step writes hidden rows
-            ch.cur_ids = torch.empty((Bp,), device=dev, dtype=torch.int64)
-            ch.out_ids = torch.empty((Bp, n_cols), device=dev, dtype=torch.int64)
-            ch.finished = torch.empty((Bp,), device=dev, dtype=torch.int32)
-            ch.pos_dev = torch.empty((1,), device=dev, dtype=torch.int32)
-            ch.step_dev = torch.empty((1,), device=dev, dtype=torch.int32)
-            ch.row_off = torch.zeros((Bp,), device=dev, dtype=torch.int32) if root.row_off is not None else None
+            ch.alloc(dev, Bp, root.out_ids.shape[1], self.lm_head.weight.shape[0], root.row_off is not None)
             ch.rows = torch.empty((Bp,), device=dev, dtype=torch.int32)
-            ch.eos, ch.pad, ch.min_new, ch.want_hidden, ch.sampling = root.eos, root.pad, root.min_new, False, root.sampling
-            ch.prefix = ch.beam = ch.trie = ch.node = ch.lp = ch.lp_norm = ch.proc = ch.cfg = ch.guided = None
-            ch.save_idx = ch.save_val = ch.stop_dev = None
-            ch.eos_all, ch.children = root.eos_all, None
+            ch.eos, ch.pad, ch.min_new, ch.sampling, ch.eos_all = root.eos, root.pad, root.min_new, root.sampling, root.eos_all
             root.children[(Bp, w8_key)] = ch
         if w8:
             self._w_used = "fp8_e4m3" if self._w_used != "bf16" else "bf16"
@@ -2551,7 +2455,94 @@ class GenerationEngine:
 
 
 class _DecodeState:
-    pass
+    """What one captured decode step reads and writes (built by _state, and by _shed_to for the children of a wave that sheds rows).  Born with
+    every attribute "absent" - None for what an option owns - so a state built anywhere takes the plain greedy step until something is set."""
+
+    def __init__(self):
+        self.key = self.graph = self.kc = self.vc = self.ws = None
+        self.B = self.S = self.Tmax = self.slot = 0
+        self.ks = self.vs = None                 # the fp32 row scales of the FP8 KV cache
+        self.w8 = self.want_hidden = False       # the step streams the FP8 weights / copies the hidden rows to hn
+        self.cur_ids = self.out_ids = self.finished = self.pos_dev = self.step_dev = self.logits = self.row_off = self.hn = None      # alloc(), _state
+        self.eos, self.pad, self.min_new, self.eos_all, self.sampling = -1, 0, 0, (-1,), None
+        self.prefix = self.beam = None           # _SharedPrefix (generate_shared_prefix, generate_beam); the ops.BeamState born with the state
+        self.trie = self.node = self.lp = self.lp_norm = None      # closed-set generation; return_logprobs
+        self.proc = self.save_idx = self.save_val = self.stop_dev = None      # processors
+        self.cfg = self.guided = self.lookup = None      # generate_guided; generate_lookup: _Lookup
+        self.children = None                     # a root state's children by (rows, weight form): {} on a state that _state built
+        self.rows = self.rows_idx = self.rows_host = None      # a child only: every row's index in the whole wave (device int32 / int64 / host)
+        self.n_real = 0                          # a child only: its rows that are rows of the wave (the rest of the rung are fillers)
+
+    def alloc(self, dev, B: int, n_cols: int, V: int, ragged: bool, logits=None):
+        """The per-row words of B rows and n_cols tokens; logits: the rows a lookup state's verify buffer already holds."""
+        self.logits = torch.empty((B, V), device=dev, dtype=torch.float32) if logits is None else logits
+        self.cur_ids = torch.empty((B,), device=dev, dtype=torch.int64)
+        self.out_ids = torch.empty((B, n_cols), device=dev, dtype=torch.int64)
+        self.finished = torch.empty((B,), device=dev, dtype=torch.int32)
+        self.pos_dev = torch.empty((1,), device=dev, dtype=torch.int32)
+        self.step_dev = torch.empty((1,), device=dev, dtype=torch.int32)
+        self.row_off = torch.zeros((B,), device=dev, dtype=torch.int32) if ragged else None
+
+
+class _Collect:
+    """What a call hands back beside the ids (the request's return_* flags), gathered while it runs and laid out at its end.  Callable as the
+    sink of _first_token and as on_step of _run_steps: the first logits are cloned once per state (n_first states), the step logits / hidden
+    rows at every call (st.logits / st.hn are the state's persistent, graph-baked buffers).  B: the rows of the whole wave (the scatter below)."""
+
+    def __init__(self, req: _Request, n_first: int = 1, B: int = 0):
+        self.req, self.n_first, self.B = req, n_first, B
+        self.first, self.steps, self.hidden, self._sl = [], [], [], None      # _sl: rows()'s kept steps, stacked once
+
+    @property
+    def on_step(self):                           # None where nothing is kept per step: the step loop then calls nothing
+        return self if (self.req.return_step_logits or self.req.return_hidden) else None
+
+    def __call__(self, st: "_DecodeState"):
+        r = self.req
+        if r.return_first_logits and len(self.first) < self.n_first:
+            self.first.append(st.logits.clone())
+        if r.return_step_logits and st.rows is not None:
+            # a child state of a wave that shed rows: its real rows under their indices in the whole wave, zeros where a row has left
+            full = torch.zeros((self.B,) + tuple(st.logits.shape[1:]), device=st.logits.device, dtype=st.logits.dtype)
+            full[st.rows_idx] = st.logits[:st.n_real]
+            self.steps.append(full)
+        elif r.return_step_logits:
+            self.steps.append(st.logits.clone())
+        if r.return_hidden:
+            self.hidden.append(st.hn.clone())
+
+    def whole(self, sts, out: torch.Tensor):
+        """The result of generate(): ids (`out`, the trimmed view, cloned: the buffer behind it is the one the next call refills), step logits,
+        hidden rows, first logits, log-probs - THIS order, not rows()'s, is the callers' contract.  sts: the call's states, in row order."""
+        r, n = self.req, out.shape[1]
+        res = [out.clone()]
+        res += [torch.stack(kept, 1)[:, :n] for on, kept in ((r.return_step_logits, self.steps), (r.return_hidden, self.hidden)) if on]
+        if r.return_first_logits:
+            res.append(self.first[0] if len(self.first) == 1 else torch.cat(self.first, 0))
+        if r.return_logprobs:
+            res.append(torch.cat([_lp_rows(st, 0, st.B, n) for st in sts], 0))
+        return res[0] if len(res) == 1 else tuple(res)
+
+    def rows(self, st: "_DecodeState", ids: torch.Tensor, r0: int, r1: int, n_done: int):
+        """What the rows r0 .. r1 of a wave return as a call of their own: their ids trimmed at THEIR EOS and cloned, then the step logits or
+        the hidden rows of the kept columns (one at a time) or else the first logits, then the log-probs, last; unwrapped when alone."""
+        r = self.req
+        out = _trim_at_eos(ids[r0:r1], n_done, st.eos_all).clone()
+        res = (out,)
+        if r.return_step_logits or r.return_hidden:
+            if self._sl is None:
+                self._sl = torch.stack(self.hidden if r.return_hidden else self.steps, 1)
+            res += (self._sl[r0:r1, : out.shape[1]].clone(),)
+        elif r.return_first_logits:
+            res += (self.first[0][r0:r1].clone(),)
+        if r.return_logprobs:
+            res += (_lp_rows(st, r0, r1, out.shape[1]),)
+        return res if len(res) > 1 else out
+
+    def groups(self, st: "_DecodeState", ids: torch.Tensor, counts, n_done: int) -> list:
+        """rows() for consecutive groups of counts[g] rows."""
+        ends = [sum(counts[:g + 1]) for g in range(len(counts))]
+        return [self.rows(st, ids, e - n, e, n_done) for n, e in zip(counts, ends)]
 
 
 def _lp_rows(st: "_DecodeState", r0: int, r1: int, n: int) -> torch.Tensor:

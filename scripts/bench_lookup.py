@@ -104,17 +104,17 @@ def _reset(st, S):
 
 
 def step_level(eng, D):
-    from crab_amd.decoder import _ws_slot
+    from crab_amd.decoder import _Request, _ws_slot
     g = torch.Generator(device=dev).manual_seed(2)
     emb = (torch.randn(1, KEYS, D, device=dev, generator=g) * 0.5).bfloat16()
     max_new = 4 * iters + 64                                     # a window of `iters` replays (+ 3 warm-up) stays far below it, k + 1 tokens per replay included
     sides = {}
     with _ws_slot(0):
-        st = eng._start(emb, max_new, None, 2, 0, 0, False, 0)
+        st = eng._start(emb, _Request(max_new, pad_token_id=2))
         sides["plain"] = (st, eng._capture(st))
     for slot, k in enumerate((3, 7, 15), start=1):
         with _ws_slot(slot):
-            st = eng._start(emb, 16 * iters + 64, None, 2, 0, 0, False, slot, lookup=(k, 2, False))
+            st = eng._start(emb, _Request(16 * iters + 64, pad_token_id=2, lookup=(k, 2, False)), slot)
             st.lookup.hist[KEYS:KEYS + 1].copy_(st.out_ids[0, :1])
             sides[f"k{k}"] = (st, eng._capture(st))
     times = {n: [] for n in sides}

@@ -15,7 +15,8 @@ g = torch.Generator(device="cuda").manual_seed(0)
 embA = (torch.randn(B, 702, D, device="cuda", generator=g) * 0.02).bfloat16()
 embB = (torch.randn(B, 702, D, device="cuda", generator=g) * 0.02).bfloat16()
 # group A: prefilled decode state + captured graph (engine internals)
-st = eng._start(embA, 256, None, 2, 0, 16, False, 0, None)
+from crab_amd.decoder import _Request
+st = eng._start(embA, _Request(256, pad_token_id=2, prefill_chunk=16))
 graph = eng._capture(st)
 kcB, vcB = eng.alloc_cache(B, 1024)
 s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()

@@ -174,11 +174,15 @@ def test_engine_refuses_by_name_before_any_device_work():
         g(emb, neg, 1.5, 4, max_rows=1)
     with pytest.raises(TypeError, match="banana"):
         g(emb, neg, 1.5, 4, banana=1)
-    # the neutral values of what is refused are the call without them: they reach the (stubbed) entry
+    # the neutral values of what is refused are the call without them: they reach the (stubbed) entry with an equal request
     reached = []
     eng._call = lambda *a, **k: reached.append(a) or "ran"
     assert g(emb, neg, 1.5, 4, processors=(1.0, 0, ()), decode_streams=1, constraint=None, return_logprobs=False) == "ran"
-    assert reached[0][4] is neg and reached[0][5:7] == (1.5, 4) and reached[0][-1] == ops.DECODE_MAX_ROWS // 2
+    assert g(emb, neg, 1.5, 4) == "ran"
+    kv, wd, shed, fn, e, n, scale, cap, req = reached[0]
+    assert (kv, wd, shed) == (None, None, None) and fn == eng._generate_guided and e is emb and n is neg
+    assert scale == 1.5 and req.max_new_tokens == 4 and cap == ops.DECODE_MAX_ROWS // 2
+    assert req == reached[1][-1] == decoder._Request(4) and reached[1][:3] + reached[1][4:-1] == reached[0][:3] + reached[0][4:-1]
 
 
 # ------------------------------------------------------------------ (d) the reference

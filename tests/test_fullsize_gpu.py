@@ -228,7 +228,8 @@ def _decode_regime_vs_cpu_oracle(crab, B):
         same_steps.append(same)
     # (2) teacher-forced on the SAME decode state and graph: prefill again (first token selected from the prefill logits), then
     # overwrite the sampled rows' current ids with the oracle's before every replay
-    eng._start(emb, n_new, None, 2, 0, 0, False, 0)
+    from crab_amd.decoder import _Request
+    eng._start(emb, _Request(n_new, pad_token_id=2))
     graph = eng._capture(st)
     errs, agree, total = [], 0, 0
     rr = torch.tensor(rows, device="cuda")

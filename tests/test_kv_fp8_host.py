@@ -101,12 +101,17 @@ def test_engine_byte_accounting_switch_and_refusals():
 
 
 def test_the_decode_state_key_separates_the_modes():
-    """A captured graph of one mode is never replayed for the other: the mode is part of _state's key (read from the source: building a state needs a device)."""
-    import inspect
-    from crab_amd.decoder import GenerationEngine
-    src = inspect.getsource(GenerationEngine._state)
-    key = src[src.index("key = ("):src.index("st = self._dec.get(slot)")]
-    assert "self._kv_mode" in key and "ks.data_ptr()" in key
+    """A captured graph of one mode is never replayed for the other: the mode and both scale pointers are terms of a decode state's key
+    (decoder._state_key: real keys from plain values, no device needed), and so is the weight mode."""
+    from crab_amd.decoder import _state_key
+    base = dict(B=2, Tmax=64, max_new_tokens=8, eos=2, pad=2, min_new_tokens=0, return_hidden=False, ptrs=(11, 12, 13, 14, 15, 16, 17), lora=True,
+                sampling=None, ragged=False, kv_mode="bf16", scale_ptrs=(0, 0), w8_key=("bf16",), logprobs=False)
+    key = lambda **kw: _state_key(**dict(base, **kw))
+    k16, k8 = key(), key(kv_mode="fp8_e4m3", scale_ptrs=(21, 22))
+    assert k16 != k8 and "bf16" in k16 and "fp8_e4m3" in k8 and 21 in k8 and 22 in k8 and ("bf16",) in k16
+    assert key(kv_mode="fp8_e4m3") != k16                                                         # the mode alone
+    assert key(kv_mode="fp8_e4m3", scale_ptrs=(23, 22)) != k8 and key(kv_mode="fp8_e4m3", scale_ptrs=(21, 23)) != k8      # either scale tensor moved
+    assert key(kv_mode="fp8_e4m3", scale_ptrs=(21, 22), w8_key=("fp8_e4m3", 31, 32)) != k8       # the weight mode
 
 
 def test_format_statement_round_trips():

@@ -161,8 +161,14 @@ def test_off_reaches_the_existing_engine_entry_with_unchanged_arguments():
     assert eng.generate(emb, 8, eos_token_id=3) == "res"
     for off in (None, False):
         assert eng.generate(emb, 8, eos_token_id=3, shed_finished=off, shed_every=1) == "res"
-    assert len(seen) == 3 and all(s[0][2] == eng._generate and "shed" not in s[1] for s in seen)
-    assert all(len(s[0]) == len(seen[0][0]) and s[1].keys() == seen[0][1].keys() for s in seen[1:])
+    # (kv_cache_dtype, weight_dtype, the call's _Shed, fn, embeds, request, decode_streams): no _Shed, and the request of the plain call
+    assert len(seen) == 3 and all(s[0][2] is None and s[0][3] == eng._generate and s[0][5].shed is None and not s[1] for s in seen)
+    assert all(len(s[0]) == len(seen[0][0]) and s[0][5] == seen[0][0][5] and s[0][6] == seen[0][0][6] for s in seen[1:])
+    assert seen[0][0][5] == decoder._Request(8, 3)
+    assert eng.generate(emb, 8, eos_token_id=3, shed_finished=(2, 4), shed_every=3) == "res"
+    shed = seen[3][0][2]
+    assert isinstance(shed, decoder._Shed) and (shed.ladder, shed.every) == ((2, 4), 3) and seen[3][0][5].shed is shed
+    assert seen[3][0][5].replace(shed=None) == seen[0][0][5]
     assert decoder.check_shed(None) is None and decoder.check_shed(False, 1, return_logprobs=True) is None
     assert decoder.check_shed(True) == (decoder.shed_default_ladder(), decoder.EOS_CHECK_EVERY) and decoder.check_shed((2, 4), 3) == ((2, 4), 3)
 

@@ -2,7 +2,6 @@
 the keys that keep a captured graph inside its mode, the quantised-weight cache of a packed group, and the mixed emulation of the oracle
 (tests/w8_ref.py: prefill with W, decode steps with the dequantised weights)."""
 import ctypes as C
-import inspect
 import os
 import re
 
@@ -127,15 +126,26 @@ def test_mode_switches_and_refusals():
 
 def test_state_key_and_layer_table_fingerprint_separate_the_modes(monkeypatch):
     """A captured graph of one weight mode is never replayed for the other: the mode and the pointers of the codes / scales are part of
-    _state's key (read from the source: building a state needs a device) and of the native sequencer's layer-table fingerprint."""
-    from crab_amd.decoder import GenerationEngine
-    src = inspect.getsource(GenerationEngine._state)
-    key = src[src.index("        key = ("):src.index("st = self._dec.get(slot)")]
-    assert "w8_key" in key and "self._kv_mode" in key
-    w8k = src[src.index("w8_key = "):src.index("        key = (")]
-    assert '"fp8_e4m3"' in w8k and "_quantized()" in w8k and "data_ptr()" in w8k and '("bf16",)' in w8k
+    a decode state's key (decoder._state_key over the engine's _w8_key: real keys, no device needed) and of the native sequencer's
+    layer-table fingerprint."""
+    from crab_amd.decoder import _child_key, _state_key
     _cpu_quantiser(monkeypatch)
     eng = _tiny().base_model.model._engine
+    um8 = _tiny(weight_dtype="fp8_e4m3").base_model.model
+    eng8 = um8._engine
+    base = dict(B=2, Tmax=64, max_new_tokens=8, eos=2, pad=2, min_new_tokens=0, return_hidden=False, ptrs=(11, 12, 13, 14, 15, 16, 17), lora=True,
+                sampling=None, ragged=False, kv_mode="bf16", scale_ptrs=(0, 0), logprobs=False)
+    key = lambda **kw: _state_key(**dict(base, **kw))
+    assert eng._w8_key(2) == ("bf16",) and eng8._w8_key(17) == ("bf16",)         # the bf16 fragment; above 16 rows the FP8 mode steps on bf16 too
+    w8k = eng8._w8_key(2)
+    quant = [t.data_ptr() for l in um8.model.layers for g in l.groups() for t in g.quantize_fp8()]
+    assert w8k == ("fp8_e4m3",) + tuple(quant) and w8k == eng8._w8_key(16)        # the mode, then codes and scales of every group
+    k16, k8 = key(w8_key=("bf16",)), key(w8_key=w8k)
+    assert k16 != k8 and ("bf16",) in k16 and w8k in k8
+    assert key(w8_key=w8k[:-1] + (w8k[-1] + 256,)) != k8                          # a scale tensor that moved: another key
+    assert key(w8_key=("bf16",), kv_mode="fp8_e4m3") != k16                      # the KV mode ...
+    assert key(w8_key=("bf16",), scale_ptrs=(5, 0)) != k16 and key(w8_key=("bf16",), scale_ptrs=(0, 5)) != k16      # ... and both of its scale pointers
+    assert _child_key(k16, 4, w8k) == k16 + ("shed", 4) + w8k                     # a shed child: the root's key, its rows, ITS weight form
     fp16, fp8 = eng._table_fingerprint(False), eng._table_fingerprint(True)
     assert fp16 != fp8 and fp8[:len(fp16)] == fp16 and "fp8_e4m3" in fp8
     n_groups = 4 * len(eng.model.layers)
