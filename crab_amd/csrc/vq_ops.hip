@@ -7,7 +7,7 @@
 //   upsample_nearest2x     F.interpolate(scale_factor=2, mode="nearest") (modules.py:50)
 //   softmax_rows           AttnBlock softmax over keys (single head of C = 512 channels: scores come from the GEMM)
 //   row_sqnorm / vq_argmin nearest codebook entry: argmin_n |e_n|^2 - 2 z.e_n (the |z|^2 term of quantize.py:286-288 is
-//                          constant per row), first minimum wins like torch.argmin
+//                          constant per row), first minimum wins like torch.argmin (a NaN distance counts as the minimum: vq_before)
 #include "common.h"
 #include "crab_internal.h"
 #include <math.h>
@@ -170,6 +170,16 @@ __global__ void row_sqnorm_kernel(const bf16_t* __restrict__ e, long lde, int N,
     if (lane == 0) out[n] = s;
 }
 
+// The order torch.argmin puts candidates (value, index) in: a NaN below every number, then the smaller value, then the smaller index - so a NaN
+// counts as the minimum and the first one wins (as mask_labels_kernel does for arg-max), and a row that is +inf throughout gives its first entry.
+// The starting candidate (+inf, 0x7fffffff) loses to every real entry, +inf included, by its index; it used to survive a row without a finite
+// distance (strict < against +inf, NaN never below anything) and left 0x7fffffff + offset as the id.
+__device__ __forceinline__ bool vq_before(float v, int i, float b, int bi) {
+    const bool vn = v != v, bn = b != b;
+    if (vn != bn) return vn;
+    return (vn || v == b) ? i < bi : v < b;
+}
+
 // one block per row: idx = first argmin_n (e2[n] - 2 dots[m][n])
 __global__ __launch_bounds__(256) void vq_argmin_kernel(const float* __restrict__ dots, long ldd, const float* __restrict__ e2, int N,
                                                         int64_t* __restrict__ idx, int64_t offset) {
@@ -180,19 +190,19 @@ __global__ __launch_bounds__(256) void vq_argmin_kernel(const float* __restrict_
     float best = INFINITY; int besti = 0x7fffffff;
     for (int n = tid; n < N; n += 256) {
         const float v = e2[n] - 2.0f * d[n];
-        if (v < best) { best = v; besti = n; }                    // ascending n per thread: first minimum kept
+        if (vq_before(v, n, best, besti)) { best = v; besti = n; }  // ascending n per thread: first minimum kept
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float ov = __shfl_xor(best, o, 64);
         const int oi = __shfl_xor(besti, o, 64);
-        if (ov < best || (ov == best && oi < besti)) { best = ov; besti = oi; }
+        if (vq_before(ov, oi, best, besti)) { best = ov; besti = oi; }
     }
     if (lane == 0) { bv[wv] = best; bi[wv] = besti; }
     __syncthreads();
     if (tid == 0) {
         for (int k = 1; k < 4; ++k)
-            if (bv[k] < best || (bv[k] == best && bi[k] < besti)) { best = bv[k]; besti = bi[k]; }
+            if (vq_before(bv[k], bi[k], best, besti)) { best = bv[k]; besti = bi[k]; }
         idx[blockIdx.x] = (int64_t)besti + offset;
     }
 }
@@ -203,7 +213,7 @@ __global__ __launch_bounds__(256) void vq_argmin_kernel(const float* __restrict_
 // fp32 only where it is below fp32 summation noise.  2 M N D flops (2.1 GF per 256 x 256 mask: irrelevant next to the encoder), vector FMAs.
 // grid (ceil(M / 16), nsplit): a block owns 16 latent rows (LDS, broadcast reads) and every nsplit-th 64-entry tile of the codebook (staged through
 // LDS, row stride D + 1: conflict-free); a wave owns 4 of the rows, a lane one entry of the tile; k ascends in both the dot product and the
-// tile walk, so a thread meets its entries in ascending n (first minimum kept by strict <).  part[m][split] = (best d, its n).
+// tile walk, so a thread meets its entries in ascending n (first minimum kept: vq_before).  part[m][split] = (best d, its n).
 constexpr int VQ_RT = 16, VQ_NT = 64, VQ_MAXD = 256;
 
 __global__ __launch_bounds__(256) void vq_nearest_f32_kernel(const float* __restrict__ z, long ldz, const float* __restrict__ e, long lde,
@@ -255,7 +265,7 @@ __global__ __launch_bounds__(256) void vq_nearest_f32_kernel(const float* __rest
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const float dv = (z2s[wv * 4 + j] + en) - 2.0f * acc[j];
-                if (dv < best[j]) { best[j] = dv; besti[j] = n; }
+                if (vq_before(dv, n, best[j], besti[j])) { best[j] = dv; besti[j] = n; }
             }
         }
     }
@@ -266,7 +276,7 @@ __global__ __launch_bounds__(256) void vq_nearest_f32_kernel(const float* __rest
         for (int o = 32; o > 0; o >>= 1) {
             const float ov = __shfl_xor(b, o, 64);
             const int oi = __shfl_xor(bi, o, 64);
-            if (ov < b || (ov == b && oi < bi)) { b = ov; bi = oi; }
+            if (vq_before(ov, oi, b, bi)) { b = ov; bi = oi; }
         }
         const int m = m0 + wv * 4 + j;
         if (lane == 0 && m < M) { pbest[(long)m * nsplit + split] = b; pidx[(long)m * nsplit + split] = bi; }
@@ -281,7 +291,7 @@ __global__ void vq_nearest_finish_kernel(const float* __restrict__ pbest, const 
     for (int s = 0; s < nsplit; ++s) {
         const float v = pbest[(long)m * nsplit + s];
         const int i = pidx[(long)m * nsplit + s];
-        if (v < b || (v == b && i < bi)) { b = v; bi = i; }
+        if (vq_before(v, i, b, bi)) { b = v; bi = i; }
     }
     idx[m] = (int64_t)bi + offset;
 }

@@ -4,7 +4,8 @@ row-broadcast add, the previous-mask gate, the group mean, the PNG label map, th
 fuzz_ops.py does not reach (nearest upsampling, the two row softmaxes, codebook norms, the bf16-path arg-min) and the eval loops' metrics of
 csrc/seg_metrics.hip (mask_iou / metric_s_for_null / Eval_Fmeasure / calc_color_miou_fscore / color_mask_to_label) against torch and against
 oracle/metrics_oracle.py (test infrastructure, pinned to the reference's own functions by tests/golden/seg_metrics.npz).  Copies, index work and
-pixel counts must be EQUAL; floating-point values within the rounding of their output format.   python scripts/fuzz_seg.py [cases] [seed]"""
+pixel counts must be EQUAL (the batched row copy included); floating-point values: fp64 references on the GPU, every element against the derived
+bound of tests/fuzz_bounds.py (no tolerance constant here); outputs a caller owns sit inside sentinel guards.   python scripts/fuzz_seg.py [cases] [seed]"""
 import os, random, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -12,17 +13,29 @@ import torch
 import torch.nn.functional as F
 from crab_amd import ops, _lib, avss_utils as AU, harness
 from oracle import metrics_oracle as MO
+from tests import fuzz_bounds as FB
 
 BF = torch.bfloat16
 NCASE = int(sys.argv[1]) if len(sys.argv) > 1 else 300
 rng = random.Random(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
-bad, rejected, done, why, worst = [], 0, 0, {}, {}
+bad, rejected, done, why, worst, ratios = [], 0, 0, {}, {}, {}
+run = FB.Run()                                        # the floating-point kinds: every element against its derived bound
+S = 777.0
 KINDS = ["im2col", "im2col_strided", "pixel_shuffle", "bilinear", "dense_pe", "add_rows", "mask_gate", "group_mean", "mask_labels", "act",
-         "upsample", "softmax", "sqnorm", "vq_argmin", "mask_iou", "fmeasure", "miou_fscore", "color_to_label"]
+         "upsample", "softmax", "sqnorm", "vq_argmin", "mask_iou", "fmeasure", "miou_fscore", "color_to_label", "copy_batched"]
 
 
-def relerr(a, b):
-    return float((a.float() - b.float()).abs().max()) / (float(b.float().abs().max()) + 1e-9)
+def guarded(M, N, dtype, gap):
+    buf = torch.full((M + 2, N + gap), S, device="cuda", dtype=dtype)
+    return buf, buf[1:M + 1, :N]
+
+
+def intact(buf, N):
+    return bool((buf[0] == S).all()) and bool((buf[-1] == S).all()) and bool((buf[:, N:] == S).all())
+
+
+def judge(what, got, ref, bound):
+    ratios[kind] = max(ratios.get(kind, 0.0), run.judge(bad, desc, what, got, ref, bound))
 
 
 def tokens(x):                                        # [B, C, h, w] -> token-major [B*h*w, C]
@@ -41,7 +54,7 @@ def close64(a, b, rel=1e-6):
 for case in range(NCASE):
     g = torch.Generator(device="cuda").manual_seed(case)
     kind = rng.choice(KINDS)
-    desc, err, tol = f"case {case}: {kind}", 0.0, 0.0
+    desc, err, tol, ok_guard = f"case {case}: {kind}", 0.0, 0.0, True
     rn = lambda *s: torch.randn(*s, device="cuda", generator=g)
     try:
         if kind in ("im2col", "im2col_strided"):
@@ -81,43 +94,43 @@ for case in range(NCASE):
             strides = (1, w * C, C) if tm else (h * w, w, 1)
             alpha, beta = rng.choice([1.0, 0.5]), rng.choice([0.0, 0.0, 1.0, 0.25])
             out0 = rn(C, H, W)
-            out = out0.clone()
-            ops.bilinear(store, strides, C, h, w, out, alpha, beta)
-            want = beta * out0 + alpha * F.interpolate(x.float()[None], size=(H, W), mode="bilinear", align_corners=False)[0]
-            err, tol = relerr(out, want), 2e-6
+            if beta == 0.0: out0.fill_(float("nan"))                                            # beta = 0 must not read the output (the SegModule passes torch.empty)
+            buf, rows = guarded(C, H * W, torch.float32, 0)
+            out = rows.view(C, H, W)
+            out.copy_(out0)
             desc += f" C={C} {h}x{w}->{H}x{W} fp32={f32} token_major={tm} alpha={alpha} beta={beta}"
+            ops.bilinear(store, strides, C, h, w, out, alpha, beta)
+            judge("bilinear", out, *FB.bilinear_bound(store, strides, h, w, H, W, alpha, beta, out0))
+            ok_guard = intact(buf, H * W)
         elif kind == "dense_pe":
             h, w, Fq = rng.choice([1, 7, 28, 64]), rng.choice([1, 9, 28, 64]), rng.choice([1, 16, 128])
-            G = rn(2, Fq)
-            got = ops.dense_pe(G, h, w)
-            ys, xs = (torch.arange(h, device="cuda").float() + 0.5) / h, (torch.arange(w, device="cuda").float() + 0.5) / w
-            c = torch.stack([xs[None, :].expand(h, w), ys[:, None].expand(h, w)], -1)           # (x, y)
-            a = 2 * np.pi * ((2 * c - 1).double() @ G.double())
-            want = torch.cat([a.sin(), a.cos()], -1).reshape(h * w, 2 * Fq).float()
-            err, tol = float((got.float() - want).abs().max()), 4.1e-3 + 2e-5 * float(a.abs().max())      # bf16 output + fp32 argument rounding of sin / cos
+            G = rn(2, Fq) * rng.choice([1.0, 1.0, 10.0])
             desc += f" h={h} w={w} F={Fq}"
+            judge("dense_pe", ops.dense_pe(G, h, w), *FB.dense_pe_bound(G, h, w))
         elif kind == "add_rows":
             M, D, br = rng.choice([1, 5, 64, 300, 1024]), rng.choice([8, 64, 256, 1000]), rng.choice([1, 3, 64])
             a, b = rn(M, D + 8).to(BF)[:, :D], rn(br, D).to(BF)
-            got = ops.add_rows(a, b)
+            buf, got = guarded(M, D, BF, rng.choice([0, 8]))
+            ops.add_rows(a, b, out=got)
             want = (a.float() + b.float()[torch.arange(M, device="cuda") % br]).to(BF)
             err = float((got.view(torch.int16) != want.view(torch.int16)).sum())
+            ok_guard = intact(buf, D)
             desc += f" M={M} D={D} brows={br}"
         elif kind == "mask_gate":
             M, D, nc = rng.choice([1, 3, 4, 5, 784]), rng.choice([1, 32, 100, 256]), rng.choice([1, 2, 71, 130])
             prev, src = (rn(M, nc) * 3).to(BF), rn(M, D).to(BF)
-            want = (src.float() * (torch.sigmoid(prev.float().mean(1, keepdim=True)) + 1)).to(BF)
-            got = ops.mask_gate(prev, src.clone())
-            err, tol = relerr(got, want), 8e-3
             desc += f" M={M} D={D} classes={nc}"
+            buf, got = guarded(M, D, BF, rng.choice([0, 3]))
+            got.copy_(src)
+            ops.mask_gate(prev, got)
+            judge("mask_gate", got, *FB.mask_gate_bound(prev, src))
+            ok_guard = intact(buf, D)
         elif kind == "group_mean":
             G_, T, D = rng.choice([1, 6, 71]), rng.choice([1, 2, 6, 10]), rng.choice([1, 8, 256, 4096])
             x = rn(G_ * T, D).to(BF)
             sc = rng.choice([1.0, 1.0 / T])
-            got = ops.group_mean(x, G_, T, sc)
-            want = (sc * x.float().view(G_, T, D).sum(1)).to(BF)
-            err, tol = relerr(got, want), 8e-3
             desc += f" G={G_} T={T} D={D}"
+            judge("group_mean", ops.group_mean(x, G_, T, sc), *FB.group_mean_bound(x, T, sc))
         elif kind == "mask_labels":
             C, H, W = rng.choice([1, 2, 71, 255]), rng.choice([1, 7, 224]), rng.choice([1, 13, 224])
             pred = rn(C, H, W)
@@ -132,11 +145,8 @@ for case in range(NCASE):
         elif kind == "act":
             n, act = rng.choice([1, 7, 256, 100003]), rng.choice(["gelu", "quick_gelu", "relu", "silu"])
             x = (rn(n) * 3).to(BF)
-            xf = x.float()
-            want = {"gelu": F.gelu(xf), "quick_gelu": xf * torch.sigmoid(1.702 * xf), "relu": F.relu(xf), "silu": F.silu(xf)}[act]
-            got = ops.act_inplace(x.clone(), act)
-            err, tol = float((got.float() - want).abs().max()) / (float(want.abs().max()) + 1e-9), 4.5e-3
             desc += f" n={n} {act}"
+            judge("act", ops.act_inplace(x.clone(), act), *FB.act_bound(x, act))
         elif kind == "upsample":
             B, h, w, C = rng.choice([1, 2]), rng.choice([1, 3, 16]), rng.choice([1, 5, 16]), rng.choice([8, 64, 136])
             x = rn(B, C, h, w).to(BF)
@@ -149,13 +159,15 @@ for case in range(NCASE):
             x = (rn(M, N + 3) * rng.choice([1.0, 30.0]))[:, :N]
             sc = rng.choice([1.0, 0.125])
             if rng.random() < 0.3: x[0, 0] = 3.0e4                                               # one dominant entry: exp of the rest underflows
-            want = torch.softmax(sc * x.double(), -1).float()
-            if rng.random() < 0.5:
-                got, tol = ops.softmax_rows_f32(x, sc), 3e-6
+            f32 = rng.random() < 0.5
+            desc += f" M={M} N={N} scale={sc} fp32={f32}"
+            if f32:
+                got = ops.softmax_rows_f32(x, sc)
             else:
-                got, tol = ops.softmax_rows(x, sc).float(), 4.1e-3
-            err = float((got - want).abs().max()) / (float(want.max()) + 1e-30)
-            desc += f" M={M} N={N} scale={sc}"
+                buf, got = guarded(M, N, BF, rng.choice([0, 5]))                                  # an [M, N] view of a wider buffer
+                ops.softmax_rows(x, sc, out=got)
+                ok_guard = intact(buf, N)
+            judge("softmax", got, *FB.softmax_rows_bound(x, sc, out_bf16=not f32))
         elif kind == "sqnorm":
             N, D = rng.choice([1, 3, 4, 5, 1000, 16384]), rng.choice([1, 4, 8, 256, 300])
             if rng.random() < 0.5:
@@ -164,9 +176,8 @@ for case in range(NCASE):
             else:
                 e = rn(N, D + 8).to(BF)[:, :D]
                 got = ops.row_sqnorm(e)
-            want = (e.double() ** 2).sum(1).float()
-            err, tol = relerr(got, want), 2e-6
             desc += f" N={N} D={D} {e.dtype}"
+            judge("sqnorm", got, *FB.sqnorm_bound(e))
         elif kind == "vq_argmin":
             M, N = rng.choice([1, 5, 256, 1000]), rng.choice([1, 2, 255, 256, 257, 16384])
             dots, e2 = rn(M, N + 1)[:, :N], rn(N).abs()
@@ -220,6 +231,27 @@ for case in range(NCASE):
             ok = ok and close64(torch.stack(vid).cpu().numpy(), vw)
             err = 0.0 if ok else 1.0
             desc += f" BF={BFr} C={C} {H}x{W} {mode}"
+        elif kind == "copy_batched":
+            batch, rows, cols = rng.choice([1, 3]), rng.choice([1, 5, 32, 257]), rng.choice([8, 24, 256, 1024])
+            form = rng.choice(["broadcast", "drop first row", "strided rows"])
+            gap = rng.choice([0, 8])                                                             # ldd > cols
+            buf, dst = guarded(batch * rows, cols, BF, gap)
+            ldd = buf.stride(0)
+            if form == "broadcast":                                                              # sbs = 0: the query tokens of every sample
+                src = rn(rows, cols).to(BF)
+                ops.copy_rows_batched(src, cols, 0, dst, ldd, rows * ldd, batch, rows, cols)
+                want = src.repeat(batch, 1)
+            elif form == "drop first row":                                                       # an offset source view, sbs = (rows + 1) cols
+                full = rn(batch, rows + 1, cols).to(BF)
+                ops.copy_rows_batched(full[:, 1:], cols, (rows + 1) * cols, dst, ldd, rows * ldd, batch, rows, cols)
+                want = full[:, 1:].reshape(batch * rows, cols)
+            else:                                                                                # lds > cols on the source as well
+                full = rn(batch, rows, cols + 16).to(BF)
+                ops.copy_rows_batched(full[:, :, 8:], cols + 16, rows * (cols + 16), dst, ldd, rows * ldd, batch, rows, cols)
+                want = full[:, :, 8:8 + cols].reshape(batch * rows, cols)
+            err = float((dst.view(torch.int16) != want.view(torch.int16)).sum())
+            ok_guard = intact(buf, cols)
+            desc += f" batch={batch} rows={rows} cols={cols} {form} gap={gap}"
         else:
             n, H, W = rng.choice([1, 2, 71, 256]), rng.choice([1, 7, 224]), rng.choice([1, 5, 224])
             pal = harness.default_palette(max(n, 71))[:n] if n <= 71 else np.random.RandomState(case).randint(0, 256, (n, 3)).astype(np.uint8)
@@ -242,8 +274,10 @@ for case in range(NCASE):
     n_, w_ = worst.get(kind, (0, 0.0))
     worst[kind] = (n_ + 1, max(w_, err))
     if not (err <= tol): bad.append(desc + f" -> err {err:.3e} (tol {tol})")
-print("  per kind (cases, worst error): " + ", ".join(f"{k} {n} {w:.1e}" for k, (n, w) in sorted(worst.items())))
-print(f"{done} cases computed, {rejected} rejected by the library, {len(bad)} failures")
+    if not ok_guard: bad.append(desc + " -> a store landed outside the output block")
+print("  per kind (cases, mismatches of the equality kinds): " + ", ".join(f"{k} {n} {w:.0f}" for k, (n, w) in sorted(worst.items())))
+print("  per kind, worst err / bound: " + ", ".join(f"{k} {r:.3f}" for k, r in sorted(ratios.items())))
+print(f"{done} cases computed, {rejected} rejected by the library, {len(bad)} failures; floating-point kinds: {run}")
 for k_, v_ in sorted(why.items(), key=lambda kv: -kv[1]): print(f"  rejected x{v_}: {k_}")
 for b_ in bad[:40]: print("FAIL", b_)
 sys.exit(1 if bad else 0)

@@ -1,5 +1,5 @@
 """fp64 references and DERIVED per-element error bounds for the differential fuzzers (scripts/fuzz_gemm.py, fuzz_attn.py, fuzz_ops.py,
-fuzz_rope_epilogue.py) and tests/test_c_abi_gpu.py.  Imports only torch; runs on any device; restates no kernel: a reference here is the plain
+fuzz_rope_epilogue.py, fuzz_seg.py), tests/test_c_abi_gpu.py, tests/test_pixel_ops_gpu.py and the kernel tests of tests/test_vqgan.py.  Imports only torch; runs on any device; restates no kernel: a reference here is the plain
 operation in fp64 on the operands the kernel was given, and a bound is the largest error the kernel's arithmetic can legitimately leave on an
 element.  No bound is computed from the output under test.  Every number comes from the operands and the fp64 reference, from
 U = 2^-9 and U32 = 2^-24, or from TOL_F32 (shared with tests/test_ops_gpu.py).
@@ -102,10 +102,74 @@ RoPE epilogue, fused against unfused beyond 256 rows (dec2_choose may slice K di
     g = bf16(y + c) - bf16(y - c).  Through the rotation (|cos| g_own + |sin| g_partner =: D, at most sqrt(2) max(g)) and the second
     rounding:  |a - b| <= D + 2 (half_ulp(|o_ref| + D)) + 6 U32 (|cos x| + |sin x'|), and 0 (bit-identical) where D = 0.
     (One bf16 ulp of the outputs, 2^-7 max(|a|, |b|), is the second rounding alone; it is not a bound where the rotation cancels.)
+
+Pixel path (csrc/seg_ops.hip, csrc/vq_ops.hip).  A scalar argument (scale, eps, alpha, beta) reaches a kernel as a C float: the references take
+its fp32 value (f32_arg), the operand the kernel was given.  Operation counts are read off the kernels' loops.
+
+Row softmax (softmax_rows_kernel bf16 out / softmax_rows_f32_kernel), p_j = exp(s_j - m) / l, s = scale x.
+    The product scale x_j is rounded once (or not at all where the compiler contracts it into the subtraction): |fp32(s_j) - s_j|, taken exactly
+    from the operands (0 for a power-of-two scale).  The maximum is the same rounded value in numerator and denominator and cancels.  The
+    subtraction and the log2(e) product of __expf move the argument by 2 U32 |s_j - m|, the exponential itself by one ulp (2 U32):
+        a_j = |fp32(s_j) - s_j| + (2 |s_j - m| + 2) U32                                      (relative, on p~_j)
+    The row sum moves by sum_k p_k a_k (each term by its own a_k) and by its own roundings: a thread adds ceil(N / 256) terms in series, 6
+    butterfly levels, 3 additions of the 4 wave partials; 1 / l and the product p~ / l: 3 more (c = 12).
+        f32_j = 1.01 (a_j + sum_k p_k a_k + (ceil(N / 256) + 12) U32) p_j + 2^-126
+    (1.01: second order; every a_j that meets a p_j > 0 is below 2^-10.)  The smallest normal is added because an fp32 result below it may be
+    flushed to 0: an entry whose exact value underflows is held to 2^-126, not to 0.  bf16 output: stored(p, f32).
+
+In-place activation (act_kernel): bf16(act(x)) with apply_act, the GEMM epilogue's function: stored(act64(x), act_eval(x)).
+
+Previous-mask gate (mask_gate_kernel): src (sigmoid(mean_c prev) + 1).  A lane adds ceil(ncls / 64) bf16 values in series, then 6 butterfly
+    levels and the division: d_mean = ((ceil(ncls / 64) + 6) mean|prev| + |mean|) U32.  e = expf(-mean) moves by d_mean + 2 U32 relative;
+    sig = 1 / (1 + e): the sum and the reciprocal 3 U32, and e weighs (1 - sig) in it; the + 1 one rounding of g = sig + 1:
+        d_g = sig ((1 - sig)(d_mean + 2 U32) + 3 U32) + U32 g;      stored(src g, |src| d_g + U32 |src g|).
+
+Group mean (group_mean_kernel): bf16(scale sum_{k < T} x_k): T - 1 serial additions and the product - stored(ref, (T + 1) U32 |scale| sum|x|).
+
+Row square norms (row_sqnorm_kernel / row_sqnorm_f32_kernel): a lane adds ceil(D / 64) squares in series (exact for bf16 rows, one rounding each
+    for fp32 rows), 6 butterfly levels: (ceil(D / 64) + 7) U32 sum e^2, fp32 output.
+
+Dense positional encoding (dense_pe_kernel): [sin a | cos a], a = 2 pi (cx G0 + cy G1), c = 2 (i + 1/2) / n - 1 from the definition in fp64.
+    The fp32 coordinate: a division and a subtraction, 3 U32 absolute (|c| <= 1); the two products and the sum U32 (|G0| + |G1|) + U32 |t|; the
+    fp32 constant 2 pi and its product 2 U32 |a|:  d_a <= U32 (3 |a| + 8 pi (|G0| + |G1|)) <= 4 U32 (|a| + 2 pi (|G0| + |G1|)).
+    sin / cos have slope <= 1 and sinf / cosf are good to 2 ulp of a value <= 1 (4 U32): stored(ref, d_a + 4 U32).
+
+Bilinear resize (bilinear_kernel, align_corners = False): f = (i + 1/2) n_in / n_out - 1/2 clamped at 0, i0 = floor f, i1 = min(i0 + 1, n_in - 1),
+    weight l = f - i0, all in fp64 from the definition.  The fp32 f carries the ratio's rounding, the product and the subtraction:
+    d_f = 3 U32 (|f| + 1).  The interpolant is continuous and piecewise linear in f, so d_f enters times the slope - of the segment the fp64 f
+    lies in or, where f is within d_f of a knot and the kernel lands on the other side, of a neighbouring one: S = the largest |v(k + 1) - v(k)|
+    over the segments i0 - 1, i0, i0 + 1 (at the two columns / rows that take part).  The weights 1 - l, four products and three sums:
+    6 U32 T, T the sum of the absolute terms.  d_v = 1.01 (d_fy S_y + d_fx S_x + 6 U32 T) (1.01: the cross terms).  out = beta out0 + alpha v:
+    two products and a sum - bound = |alpha| d_v + 3 U32 (|beta out0| + |alpha| T); fp32 output, no store rounding.  beta = 0 does not read out0.
+
+GroupNorm (groupnorm_stats_kernel + the three apply kernels; bf16 or fp32 rows, bf16 or fp32 parameters, bf16 or fp32 output).
+    Statistics over n = HW C/G values of v = x - k, k the group's first value of the image (the shifted form).  A thread adds rows_per_chunk
+    values of a channel in series, one thread then C/G channel sums, the apply pass at most 64 chunk sums: depth L = rows_per_chunk + C/G + chunks
+    (chunks = min(64, ceil(HW / 64)), re-derived from the rounded-up rows as the launcher does).  With v's own rounding and the division:
+        d_mean = ((L + 2) E|v| + |mean|) U32            (mean = E v + k, one more rounding)
+        d_var  = ((L + 3) E v^2 + 2 |E v| (L + 2) E|v| + 2 (E v^2 + (E v)^2)) U32          (var = E v^2 - (E v)^2)
+    - relative to E|x - k| and E (x - k)^2, not to E|x| and E x^2: what the unshifted form would owe.  rstd = rsqrtf(var + eps):
+    r_rstd = d_var / (2 (var + eps)) + 3 U32.  y = (x - mean) rstd w + b:
+        f32 = 1.01 [ ((d_mean + U32 |xc|) rstd + |xc| rstd (r_rstd + 2 U32)) |w| + U32 |y| ]
+    swish: LIP f32 + act_eval(y).  fp32 output: f32; bf16 output: stored(y, f32).  Parameters are taken as given (bf16 or fp32, both exact in fp32).
+
+Split-operand GEMM (split3_kernel + crab_gemm_bf16 over 3K): the reference is the exact x w^T; what the form itself leaves out (the lo.lo term and
+    the 16-bit split) is |exact - T64| with T64 = hi.hi + lo.hi + hi.lo in fp64, hi = bf16(x), lo = bf16(x - hi); the 3K exact products are added in
+    fp32 in some order: bound = |exact - T64| + (3K + 2) U32 A, A the sum of the absolute products of the three terms.
+
+fp32 quantiser (vq_nearest_f32_kernel): d_mn = (|z_m|^2 + |e_n|^2) - 2 z_m . e_n in fp32.  The two square norms: a lane adds ceil(D / 64) squares,
+    log2(min(D, 64)) butterfly levels that add non-zero terms, the square's rounding; the dot product D serial FMAs; two more roundings for the
+    sum and the difference - at most D + 3 roundings on terms bounded by |z|^2, |e_n|^2 and 2 |z| |e_n| (D >= 4):
+        delta_mn = (D + 3) U32 (|z_m|^2 + |e_n|^2 + 2 |z_m| |e_n|).
+    Entry n can be returned for row m only if d64_mn - min_n d64_mn <= delta_mn + delta_m,argmin.  A row with one such entry must return it; a
+    row with several (EITHER) may return any of THEM, nothing else.  Later copies of an identical codebook row are never a candidate: the kernel
+    computes bit-identical distances for them and the first index wins.  The share of EITHER rows of a case is capped (VQ_EITHER_CAP) on cases of
+    at least 1 / VQ_EITHER_CAP rows - below that one undecided row exceeds the cap, and such a case holds its rows to their allowed entries only.
 """
 import math
 
 import torch
+import torch.nn.functional as F
 
 U = 2.0 ** -9
 U32 = 2.0 ** -24
@@ -115,24 +179,34 @@ LAW_SLACK_CAP = 2.0 ** -10      # attn_bound_weighted under the laws of tests/at
 HOEFFDING = math.sqrt(2.0 * math.log(2.0 / 1e-12))
 LIP = {"none": 1.0, "relu": 1.0, "gelu": 1.13, "silu": 1.1, "quick_gelu": 1.1, "swiglu_pair": 1.1}
 F64 = torch.float64
+TINY = 2.0 ** -126                    # the smallest normal fp32 number
+VQ_EITHER_CAP = 1.0 / 50             # vq_margin: at most this share of a case's rows may be left to the fp32 arithmetic
+                                     # (held on cases of at least 1 / VQ_EITHER_CAP = 50 rows: below that a single undecided row exceeds it; the directed
+                                     # edge tests of at most 17 rows print the share and hold every row, undecided ones included, to its allowed entries)
+SECOND_ORDER = 1.01                  # the products of two first-order terms, each below 2^-10 where it is used (module docstring: "1.01")
 
 
 def d64(t):
     return None if t is None else t.to(F64)
 
 
+def pow2_floor(x64):
+    """2^floor(log2 |x|) of a normal fp64 x, from its exponent bits (0 at 0) - exact on every device.  (torch.frexp / torch.ldexp are not: on the
+    GPU ldexp's power of two comes out of a pow and is an ulp off for some exponents, which moved bf16_round off the hardware's rounding on up to
+    a quarter of the elements of a 0.1 N(0,1) operand; found by split_gemm_bound at K = 8.)"""
+    return (x64.abs().contiguous().view(torch.int64) & 0x7FF0000000000000).view(F64)
+
+
 def bf16_round(x64):
     """fp64 -> the nearest bf16 number (8 significant bits, ties to even), as fp64; in one rounding (a cast through fp32 would round twice).
     Normal range only - no operand or output here comes near bf16's exponent limits."""
-    m, e = torch.frexp(x64)
-    return torch.ldexp(torch.round(m * 256.0) / 256.0, e)
+    q = pow2_floor(x64) * 2.0 ** -7                                                  # the bf16 spacing in x's binade; x / q and the product are exact
+    return torch.where(x64 != 0, torch.round(x64 / q.clamp_min(1e-300)) * q, x64)
 
 
 def half_ulp(y64):
     """Half a bf16 ulp at |y|: U times the top of y's binade (module docstring); 0 at 0."""
-    a = y64.abs()
-    top = torch.ldexp(torch.ones_like(a), torch.frexp(a).exponent)                     # |y| = m 2^e with 1/2 <= m < 1: the top of its binade is 2^e
-    return torch.where(a > 0, U * top, torch.zeros_like(a))
+    return U * 2.0 * pow2_floor(y64)                                                   # the top of |y|'s binade is twice its power-of-two floor
 
 
 def stored(y64, delta):
@@ -188,6 +262,11 @@ def act64(z, act):
     return z
 
 
+def act_eval(z, act):
+    """What evaluating the activation in fp32 at z adds (module docstring, GEMM): (8 + 2 |z|) U32 |z|; 0 for none / relu (exact)."""
+    return (8 + 2 * z.abs()) * U32 * z.abs() if act not in ("none", "relu") else torch.zeros_like(z)
+
+
 def _gemm_parts(x, w, x2, w2, bias, act, residual):
     x, w, x2, w2, bias, residual = d64(x), d64(w), d64(x2), d64(w2), d64(bias), d64(residual)
     z = x @ w.t()
@@ -211,7 +290,7 @@ def gemm_ceiling(x, w, x2=None, w2=None, bias=None, act="none", residual=None):
     """(y64, the any-order fp32 ceiling of every output element) - module docstring."""
     z, A, K, y, r = _gemm_parts(x, w, x2, w2, bias, act, residual)
     dz = (K + 4) * U32 * A
-    ev = (8 + 2 * z.abs()) * U32 * z.abs() if act not in ("none", "relu") else torch.zeros_like(z)
+    ev = act_eval(z, act)
     if act == "swiglu_pair":
         a, b = z[:, 0::2], z[:, 1::2]
         sa = a * torch.sigmoid(a)
@@ -342,7 +421,7 @@ def attn_bound_weighted(q, k, v, scale, allow, bias=None, gate=None, kind="decod
     m = s.masked_fill(~allow, -math.inf).max(-1, keepdim=True).values
     pe = p * ((d + 3) * T + 2 * (s - m).abs() + 3).masked_fill(~allow, 0.0)            # p_j e_j; 0 on the hidden keys
     c = 2 * torch.ceil(n / 16) + 32
-    slack = 1.01 * U32 * (torch.einsum("bhst,bhtd->bhsd", pe, vv.abs()) + o.abs() * pe.sum(-1, keepdim=True) + c * (S + o.abs()) + 2 * o.abs())
+    slack = SECOND_ORDER * U32 * (torch.einsum("bhst,bhtd->bhsd", pe, vv.abs()) + o.abs() * pe.sum(-1, keepdim=True) + c * (S + o.abs()) + 2 * o.abs())
     f32 = slack
     if kind == "fwd":
         n2 = torch.einsum("bhst,bhtd->bhsd", p * p, vv * vv).sqrt()
@@ -368,3 +447,181 @@ def rope_pair_bound(y64, ceil, cos, sin):
     o = torch.cat([x[..., :h] * cos - x[..., h:] * sin, x[..., h:] * cos + x[..., :h] * sin], -1)
     b = D + 2 * half_ulp(o.abs() + D) + 6 * U32 * mag
     return torch.where(D > 0, b, torch.zeros_like(b))
+
+
+# ------------------------------------------------------------------------------------------------------------------------- pixel path
+def f32_arg(v):
+    """A scalar argument as the kernel receives it (a C float), as a Python float."""
+    return float(torch.tensor(v, dtype=torch.float32))
+
+
+def softmax_rows_bound(x, scale, out_bf16):
+    """(p64, bound) of softmax(scale x) over the last dimension of the fp32 block x - module docstring."""
+    x = d64(x)
+    N = x.shape[-1]
+    s = x * f32_arg(scale)                                                              # exact: 24 x 24 bits
+    m = s.max(-1, keepdim=True).values
+    p = torch.softmax(s, -1)
+    a = (s.float().to(F64) - s).abs() + (2 * (s - m).abs() + 2) * U32
+    f32 = SECOND_ORDER * (a + (p * a).sum(-1, keepdim=True) + (math.ceil(N / 256) + 12) * U32) * p + TINY
+    return p, (stored(p, f32) if out_bf16 else f32)
+
+
+def act_bound(x, act):
+    """(ref, bound) of bf16(act(x)) on bf16 x."""
+    x = d64(x)
+    return act64(x, act), stored(act64(x, act), act_eval(x, act))
+
+
+def mask_gate_bound(prev, src):
+    """(ref, bound) of bf16(src (sigmoid(mean_c prev) + 1)); prev [M, ncls], src [M, D]."""
+    prev, src = d64(prev), d64(src)
+    ncls = prev.shape[1]
+    mean = prev.mean(1, keepdim=True)
+    d_mean = U32 * ((math.ceil(ncls / 64) + 6) * prev.abs().mean(1, keepdim=True) + mean.abs())
+    sig = torch.sigmoid(mean)
+    g = sig + 1
+    d_g = sig * ((1 - sig) * (d_mean + 2 * U32) + 3 * U32) + U32 * g
+    ref = src * g
+    return ref, stored(ref, src.abs() * d_g + U32 * ref.abs())
+
+
+def group_mean_bound(x, T, scale):
+    """(ref, bound) of bf16(scale sum_{k < T} x[g T + k]); x [G T, D]."""
+    x, sc = d64(x), f32_arg(scale)
+    xg = x.reshape(x.shape[0] // T, T, x.shape[1])
+    ref = sc * xg.sum(1)
+    return ref, stored(ref, (T + 1) * U32 * abs(sc) * xg.abs().sum(1))
+
+
+def sqnorm_bound(e):
+    """(ref, bound) of the fp32 row sums of squares of e [N, D] (bf16 or fp32)."""
+    e = d64(e)
+    ref = (e * e).sum(1)
+    return ref, (math.ceil(e.shape[1] / 64) + 7) * U32 * ref
+
+
+def dense_pe_bound(G, h, w):
+    """(ref [h w, 2 F], bound) of the random-Fourier positional encoding of an h x w grid, G fp32 [2, F]."""
+    G = d64(G)
+    cy = (2 * (torch.arange(h, dtype=F64, device=G.device) + 0.5) / h - 1)[:, None, None]
+    cx = (2 * (torch.arange(w, dtype=F64, device=G.device) + 0.5) / w - 1)[None, :, None]
+    a = 2 * math.pi * (cx * G[0] + cy * G[1])                                          # [h, w, F]
+    d_a = 4 * U32 * (a.abs() + 2 * math.pi * (G[0].abs() + G[1].abs()))
+    ref = torch.cat([a.sin(), a.cos()], -1).reshape(h * w, -1)
+    f32 = torch.cat([d_a, d_a], -1).reshape(h * w, -1) + 4 * U32
+    return ref, stored(ref, f32)
+
+
+def _bilinear_axis(n_in, n_out, device):
+    f = (torch.arange(n_out, dtype=F64, device=device) + 0.5) * (n_in / n_out) - 0.5
+    d_f = 3 * U32 * (f.abs() + 1)
+    f = f.clamp_min(0.0)
+    i0 = f.floor().long().clamp_max(n_in - 1)
+    return i0, (i0 + 1).clamp_max(n_in - 1), f - i0, d_f
+
+
+def _segment_slope(v, dim, i0):
+    """The largest |v(k + 1) - v(k)| along dim over the segments i0 - 1, i0, i0 + 1 (absent segments count 0)."""
+    n = v.shape[dim]
+    dp = F.pad(v.diff(dim=dim).abs(), [0, 0] * (v.dim() - 1 - dim) + [1, 1])          # dp[k + 1] = segment k; n + 1 entries
+    return torch.maximum(torch.maximum(dp.index_select(dim, i0), dp.index_select(dim, i0 + 1)), dp.index_select(dim, (i0 + 2).clamp_max(n)))
+
+
+def bilinear_bound(x, strides, h, w, H, W, alpha, beta, out0):
+    """(ref [C, H, W], bound) of beta out0 + alpha resize(v), v(c, y, x) = the element of x's storage at c strides[0] + y strides[1] + x strides[2]
+    past x's first element (bf16 or fp32), out0 fp32 [C, H, W] (not read when beta = 0: it may hold anything)."""
+    C = out0.shape[0]
+    v = d64(x.as_strided((C, h, w), tuple(strides)))
+    al, be = f32_arg(alpha), f32_arg(beta)
+    y0, y1, ly, d_fy = _bilinear_axis(h, H, v.device)
+    x0, x1, lx, d_fx = _bilinear_axis(w, W, v.device)
+    ly, d_fy = ly[:, None], d_fy[:, None]
+
+    def interp(t):
+        top = (1 - lx) * t[:, y0][:, :, x0] + lx * t[:, y0][:, :, x1]
+        bot = (1 - lx) * t[:, y1][:, :, x0] + lx * t[:, y1][:, :, x1]
+        return (1 - ly) * top + ly * bot
+
+    val, T = interp(v), interp(v.abs())
+    sy = _segment_slope(v, 1, y0)                                                       # [C, H, w]
+    sx = _segment_slope(v, 2, x0)                                                       # [C, h, W]
+    Sy = torch.maximum(sy[:, :, x0], sy[:, :, x1])
+    Sx = torch.maximum(sx[:, y0], sx[:, y1])
+    d_v = SECOND_ORDER * (d_fy * Sy + d_fx * Sx + 6 * U32 * T)
+    keep = be * d64(out0) if be != 0.0 else torch.zeros_like(val)
+    return keep + al * val, abs(al) * d_v + 3 * U32 * (keep.abs() + abs(al) * T)
+
+
+def groupnorm_chunks(HW):
+    """(rows_per_chunk, chunks) as crab_groupnorm_p / crab_groupnorm_f32 launch them."""
+    chunks = min(64, -(-HW // 64))
+    rows = -(-HW // chunks)
+    return rows, -(-HW // rows)
+
+
+def groupnorm_bound(x, B, HW, G, w, b, eps, swish, out_fp32):
+    """(ref [B HW, C], bound) of GroupNorm(G, C) (+ swish) over token-major x [B HW, C] (bf16 or fp32), parameters as given - module docstring."""
+    x, e = d64(x), f32_arg(eps)
+    C = x.shape[1]
+    cpg = C // G
+    rows, chunks = groupnorm_chunks(HW)
+    L = rows + cpg + chunks
+    wg, bg = d64(w).view(G, cpg), d64(b).view(G, cpg)
+    xg = x.reshape(B, HW, G, cpg)
+    k = xg[:, :1, :, :1]
+    v = xg - k
+    Ev, Ev2, mv = v.abs().mean((1, 3), keepdim=True), v.pow(2).mean((1, 3), keepdim=True), v.mean((1, 3), keepdim=True)
+    mean = mv + k
+    xc = xg - mean
+    var = xc.pow(2).mean((1, 3), keepdim=True)
+    d_mean = U32 * ((L + 2) * Ev + mean.abs())
+    d_var = U32 * ((L + 3) * Ev2 + 2 * mv.abs() * (L + 2) * Ev + 2 * (Ev2 + mv * mv))
+    rstd = torch.rsqrt(var + e)
+    r_rstd = d_var / (2 * (var + e)) + 3 * U32
+    y = xc * rstd * wg + bg
+    f32 = SECOND_ORDER * (((d_mean + U32 * xc.abs()) * rstd + xc.abs() * rstd * (r_rstd + 2 * U32)) * wg.abs() + U32 * y.abs())
+    if swish:
+        f32 = LIP["silu"] * f32 + act_eval(y, "silu")
+        y = act64(y, "silu")
+    y, f32 = y.reshape(B * HW, C), f32.reshape(B * HW, C)
+    return y, (f32 if out_fp32 else stored(y, f32))
+
+
+def split_gemm_bound(x, w):
+    """(exact x w^T in fp64, bound) of the split-operand product gemm(split3(x, 0), split3(w, 1)) with fp32 output."""
+    x, w = d64(x), d64(w)
+    xh, wh = bf16_round(x), bf16_round(w)
+    xl, wl = bf16_round(x - xh), bf16_round(w - wh)
+    exact = x @ w.t()
+    t64 = xh @ wh.t() + xl @ wh.t() + xh @ wl.t()
+    A = xh.abs() @ wh.abs().t() + xl.abs() @ wh.abs().t() + xh.abs() @ wl.abs().t()
+    return exact, (exact - t64).abs() + (3 * x.shape[1] + 2) * U32 * A
+
+
+def vq_margin(z, e):
+    """(want [M], either [M] bool, allowed [M, N] bool) for the fp32 quantiser of z [M, D] against the codebook e [N, D], from fp64 distances and the
+    fp32 margin delta (module docstring): allowed = the entries a row may return; either = rows with more than one; want = the fp64 arg-min
+    (first copy of duplicated codebook rows), the only allowed entry of every other row."""
+    z, e = d64(z), d64(e)
+    N, D = e.shape
+    z2, e2 = (z * z).sum(1, keepdim=True), (e * e).sum(1)[None]
+    d = z2 + e2 - 2 * z @ e.t()
+    delta = (D + 3) * U32 * (z2 + e2 + 2 * z2.sqrt() * e2.sqrt())
+    _, inv = torch.unique(e, dim=0, return_inverse=True)
+    n = torch.arange(N, device=e.device)
+    first = torch.full((int(inv.max()) + 1,), N, device=e.device, dtype=n.dtype).scatter_reduce(0, inv, n, "amin")
+    dup = first[inv] != n                                                               # a later copy of an identical row
+    d = d.masked_fill(dup[None], math.inf)
+    best, want = d.min(1, keepdim=True)
+    allowed = (d - best) <= delta + delta.gather(1, want)
+    return want[:, 0], allowed.sum(1) > 1, allowed
+
+
+def vq_verdict(idx, z, e, offset=0):
+    """(rows that hold an entry they may not, share of EITHER rows) of the quantiser's ids idx [M] (offset added by the kernel)."""
+    want, either, allowed = vq_margin(z, e)
+    i = idx.to(want.device).long() - offset
+    inside = (i >= 0) & (i < e.shape[0])
+    ok = inside & allowed.gather(1, i.clamp(0, e.shape[0] - 1)[:, None])[:, 0]
+    return int((~ok).sum()), float(either.double().mean())

@@ -1,14 +1,17 @@
 """tests/fuzz_bounds.py on the CPU: the bounds the differential fuzzers judge with raise no false alarm on an fp64 emulation that has only the
 kernels' storage points (bf16 P, fp32 sums in another order, one bf16 store), under the fuzzers' own input laws at their extreme shapes - and
 they DO fail single defects applied to the reference (a key too many or too few, swapped V rows, an accumulator rounded early, a bf16 read of an
-fp32 residual, a dropped bias tile, a short K2 segment, the norm weight on the wrong side of a rounding), by a stated margin.  The last test
-pins that the fuzzers hold no tolerance literal of their own."""
+fp32 residual, a dropped bias tile, a short K2 segment, the norm weight on the wrong side of a rounding), by a stated margin.  The pixel-path bounds (row softmax, in-place
+activation, mask gate, group mean, square norms, dense positional encoding, bilinear resize, GroupNorm, the split-operand GEMM, the fp32
+quantiser's margin) get the same two assertions each: a torch fp32 emulation in another summation order passes, and the defect a global-maximum
+tolerance hid fails.  The last tests pin that the fuzzers hold no tolerance literal of their own."""
 import math
 import os
 import re
 
 import pytest
 import torch
+import torch.nn.functional as F
 
 from tests import fuzz_bounds as FB
 
@@ -313,6 +316,245 @@ def test_rope_pair_bound():
     assert _ratio(form(torch.arange(K)), b.double(), bound) > 2.0
 
 
+# ----------------------------------------------------------------------------------------------------------------------- pixel path
+ULP = 1 + 2.0 ** -7                                                         # one bf16 ulp on every element: never hidden by a bf16 output's bound
+
+
+def _softmax_emul(x, scale, f32):
+    s = x * torch.tensor(scale, dtype=torch.float32)
+    p = torch.exp(s - s.max(-1, keepdim=True).values)
+    out = p / _f32_sum_other_order(p)
+    return out if f32 else out.to(BF)
+
+
+@pytest.mark.parametrize("N,scale", [(1, 1.0), (63, 0.37), (257, 0.125), (4096, 0.125), (4096, 1.0)])
+def test_softmax_rows_bound(N, scale):
+    """No false alarm in either output format (a dominant 3e4 entry included: the rest underflows and is held to 2^-126); the fuzzer's own case
+    N = 4096, scale 0.125, x[0, 0] = 3e4 with every row but the first zeroed - which the global-maximum rule passed - fails."""
+    g = torch.Generator().manual_seed(N)
+    x = torch.randn(5, N, generator=g) * 30.0
+    x[0, 0] = 3.0e4
+    for f32 in (True, False):
+        ref, bound = FB.softmax_rows_bound(x, scale, out_bf16=not f32)
+        r = _ratio(_softmax_emul(x, scale, f32), ref, bound)
+        assert r <= 1.0, f"false alarm: N={N} scale={scale} fp32={f32}: {r:.3f}"
+        if N > 1:
+            zeroed = ref.clone(); zeroed[1:] = 0
+            assert _ratio(zeroed, ref, bound) > 2.0
+            if N < 4096: assert _ratio(torch.cat([ref[:, 1:], ref[:, :1]], 1), ref, bound) > 2.0        # columns rotated by one
+        if not f32: assert _ratio(ref * ULP, ref, bound) > 1.0
+    if N > 1: assert float(FB.softmax_rows_bound(x, scale, False)[1][0, 1:].max()) == FB.TINY          # underflowed entries: the smallest normal, not 0
+
+
+@pytest.mark.parametrize("act", ["gelu", "quick_gelu", "relu", "silu"])
+def test_act_bound(act):
+    g = torch.Generator().manual_seed(2)
+    x = _bf(torch.randn(100003, generator=g) * 3)                            # the fuzzer's law
+    xf = x.float()
+    got = {"gelu": F.gelu(xf), "quick_gelu": xf * torch.sigmoid(1.702 * xf), "relu": F.relu(xf), "silu": F.silu(xf)}[act].to(BF)
+    ref, bound = FB.act_bound(x, act)
+    assert _ratio(got, ref, bound) <= 1.0
+    if act == "gelu":
+        cut = got.clone(); cut[xf < -2] = 0                                  # worst error 0.044 against the old tolerance of 4.5e-3 max|want| = 0.056
+        assert float((cut.float() - ref).abs().max()) < 4.5e-3 * float(ref.abs().max()) and _ratio(cut, ref, bound) > 100.0
+    if act != "relu": assert _ratio(ref * ULP, ref, bound) > 1.0
+    else: assert _ratio(ref, FB.act_bound(x, "none")[0], bound) > 1.0        # relu left out
+
+
+def test_mask_gate_and_group_mean_bounds():
+    g = torch.Generator().manual_seed(3)
+    for M, nc, D in [(1, 1, 1), (5, 64, 63), (784, 65, 256), (3, 130, 100)]:
+        prev, src = _bf(torch.randn(M, nc, generator=g) * 3), _bf(torch.randn(M, D, generator=g))
+        s = prev.float().flip(-1).sum(-1, keepdim=True)
+        ref, bound = FB.mask_gate_bound(prev, src)
+        got = (src.float() * (1.0 / (1.0 + torch.exp(-(s / nc))) + 1.0)).to(BF)
+        assert _ratio(got, ref, bound) <= 1.0, (M, nc, D)
+        assert _ratio(ref * ULP, ref, bound) > 1.0
+        if nc == 65:
+            wrong = (src.float() * (torch.sigmoid(s / 64) + 1.0)).to(BF)     # the mean taken over 64, not ncls
+            assert _ratio(wrong, ref, bound) > 1.0
+            wrong = (src.float() * (torch.sigmoid(prev.float()[:, :64].sum(-1, keepdim=True) / nc) + 1.0)).to(BF)      # the 65th class dropped
+            assert _ratio(wrong, ref, bound) > 1.0
+    for G_, T, D in [(1, 1, 1), (6, 10, 256), (71, 6, 8)]:
+        x = _bf(torch.randn(G_ * T, D, generator=g))
+        for sc in (1.0, 1.0 / T):
+            ref, bound = FB.group_mean_bound(x, T, sc)
+            got = (torch.tensor(sc, dtype=torch.float32) * x.float().view(G_, T, D).flip(1).sum(1)).to(BF)
+            assert _ratio(got, ref, bound) <= 1.0, (G_, T, D, sc)
+            assert _ratio(ref * ULP, ref, bound) > 1.0
+            if T > 1:
+                short = (sc * x.float().view(G_, T, D)[:, :-1].sum(1)).to(BF)
+                assert _ratio(short, ref, bound) > 2.0
+
+
+@pytest.mark.parametrize("D", [1, 63, 65, 300])
+def test_sqnorm_bound(D):
+    g = torch.Generator().manual_seed(D)
+    for e in (torch.randn(9, D, generator=g), _bf(torch.randn(9, D, generator=g))):
+        ref, bound = FB.sqnorm_bound(e)
+        ef = e.float()
+        assert _ratio((ef * ef).flip(-1).sum(-1), ref, bound) <= 1.0
+        if D % 64 and D > 64:
+            ec = ef[:, :D - D % 64]
+            assert _ratio((ec * ec).sum(-1), ref, bound) > 2.0               # the last D % 64 elements missing
+
+
+def _dense_pe_emul(G, h, w, half=0.5, swap=False):
+    ys, xs = (torch.arange(h).float() + half) / h, (torch.arange(w).float() + half) / w
+    if swap: cx, cy = (2 * ys - 1)[:, None, None].expand(h, w, 1), (2 * xs - 1)[None, :, None].expand(h, w, 1)
+    else: cx, cy = (2 * xs - 1)[None, :, None], (2 * ys - 1)[:, None, None]
+    a = 6.283185307179586 * (cy * G[1] + cx * G[0])
+    return torch.cat([a.sin(), a.cos()], -1).reshape(h * w, -1).to(BF)
+
+
+@pytest.mark.parametrize("h,w,Fq,gs", [(1, 1, 1, 1.0), (3, 7, 16, 1.0), (28, 9, 128, 1.0), (7, 5, 16, 10.0)])
+def test_dense_pe_bound(h, w, Fq, gs):
+    g = torch.Generator().manual_seed(h * w)
+    G = torch.randn(2, Fq, generator=g) * gs
+    ref, bound = FB.dense_pe_bound(G, h, w)
+    assert _ratio(_dense_pe_emul(G, h, w), ref, bound) <= 1.0
+    assert _ratio(ref * ULP, ref, bound) > 1.0
+    assert _ratio(_dense_pe_emul(G, h, w, half=0.0), ref, bound) > 2.0       # without the + 0.5
+    if h != w: assert _ratio(_dense_pe_emul(G, h, w, swap=True), ref, bound) > 2.0
+
+
+def _bilinear_emul(v, H, W, alpha, beta, out0, corners=False, clamp=True):
+    """The kernel's expression in fp32 with the weights applied in the other order (columns first)."""
+    C, h, w = v.shape
+    def axis(n, N):
+        i = torch.arange(N, dtype=torch.float32)
+        f = i * (float(n - 1) / max(N - 1, 1)) if corners else (i + 0.5) * (torch.tensor(float(n)) / torch.tensor(float(N))) - 0.5
+        if clamp: f = f.clamp_min(0.0)
+        i0 = f.to(torch.int64).clamp(0, n - 1)                               # (int) truncates towards 0
+        return i0, (i0 + 1).clamp_max(n - 1), f - i0
+    y0, y1, ly = axis(h, H)
+    x0, x1, lx = axis(w, W)
+    v, ly = v.float(), ly[:, None]
+    left = (1 - ly) * v[:, y0][:, :, x0] + ly * v[:, y1][:, :, x0]
+    right = (1 - ly) * v[:, y0][:, :, x1] + ly * v[:, y1][:, :, x1]
+    val = (1 - lx) * left + lx * right
+    return (beta * out0 if beta != 0 else 0.0) + alpha * val
+
+
+@pytest.mark.parametrize("h,w,H,W", [(1, 1, 5, 7), (7, 5, 1, 1), (7, 5, 3, 2), (3, 5, 7, 11), (4, 6, 4, 6), (28, 28, 224, 224), (56, 3, 37, 50)])
+def test_bilinear_bound(h, w, H, W):
+    g = torch.Generator().manual_seed(h + W)
+    for bf in (False, True):
+        v = torch.randn(3, h, w, generator=g)
+        v = _bf(v) if bf else v
+        out0 = torch.randn(3, H, W, generator=g)
+        for alpha, beta in ((1.0, 0.0), (0.5, 1.0), (0.5, 0.25)):
+            ref, bound = FB.bilinear_bound(v, (h * w, w, 1), h, w, H, W, alpha, beta, out0)
+            tm = v.permute(1, 2, 0).contiguous()                             # token-major storage of the same image
+            ref2, bound2 = FB.bilinear_bound(tm, (1, w * 3, 3), h, w, H, W, alpha, beta, out0)
+            assert torch.equal(ref, ref2) and torch.equal(bound, bound2)
+            want = beta * out0 + alpha * F.interpolate(v.float()[None], size=(H, W), mode="bilinear", align_corners=False)[0]
+            assert _ratio(want, ref, bound) <= 1.0, (bf, alpha, beta)
+            assert _ratio(_bilinear_emul(v, H, W, alpha, beta, out0), ref, bound) <= 1.0, (bf, alpha, beta)
+            if (h, w) != (H, W) and h * w > 1:
+                assert _ratio(_bilinear_emul(v, H, W, alpha, beta, out0, corners=True), ref, bound) > 2.0
+            if (H > h > 1) or (W > w > 1):                                    # upsampling along an axis with more than one source row: f < 0 at the edge
+                assert _ratio(_bilinear_emul(v, H, W, alpha, beta, out0, clamp=False), ref, bound) > 2.0
+    nan0 = torch.full((3, H, W), float("nan"))
+    assert bool(torch.isfinite(FB.bilinear_bound(v, (h * w, w, 1), h, w, H, W, 0.5, 0.0, nan0)[0]).all())
+
+
+def _groupnorm_emul(x, B, HW, G, w, b, eps, swish, out_fp32, shifted=True):
+    """The kernels' arithmetic in fp32, sums in another order."""
+    C = x.shape[1]
+    xg = x.float().view(B, HW, G, C // G)
+    k = xg[:, :1, :, :1] if shifted else torch.zeros(())
+    v = (xg - k).permute(0, 2, 1, 3).reshape(B, G, -1)
+    n = v.shape[-1]
+    m = (_f32_sum_other_order(v) / n)
+    var = (_f32_sum_other_order(v * v) / n - m * m).clamp_min(0.0)
+    mean, rstd = (m.view(B, 1, G, 1) + k), torch.rsqrt(var + torch.tensor(eps, dtype=torch.float32)).view(B, 1, G, 1)
+    y = ((xg - mean) * rstd * w.float().view(G, -1) + b.float().view(G, -1)).view(B * HW, C)
+    if swish: y = y / (1.0 + torch.exp(-y))
+    return y if out_fp32 else y.to(BF)
+
+
+@pytest.mark.parametrize("C,G,HW", [(8, 8, 1), (24, 8, 65), (64, 32, 70), (1024, 32, 130), (32, 32, 4097)])
+def test_groupnorm_bound(C, G, HW):
+    g = torch.Generator().manual_seed(C + HW)
+    B = 3
+    wt, bs = 1 + 0.2 * torch.randn(C, generator=g), 0.1 * torch.randn(C, generator=g)
+    for scale, shift in ((2.0, 0.5), (0.3, 0.0), (0.01, 100.0)):
+        xf = torch.randn(B * HW, C, generator=g) * scale + shift
+        for form in ("f32", "bf16, fp32 params", "bf16, bf16 params"):
+            x = xf if form == "f32" else _bf(xf)
+            w_, b_ = (_bf(wt), _bf(bs)) if form == "bf16, bf16 params" else (wt, bs)
+            for sw in (False, True):
+                ref, bound = FB.groupnorm_bound(x, B, HW, G, w_, b_, 1e-6, sw, out_fp32=form == "f32")
+                r = _ratio(_groupnorm_emul(x, B, HW, G, w_, b_, 1e-6, sw, form == "f32"), ref, bound)
+                assert r <= 1.0, f"false alarm: C={C} G={G} HW={HW} {form} swish={sw} scale={scale}: {r:.3f}"
+                if form != "f32" and shift < 100.0: assert _ratio(ref * ULP, ref, bound) > 1.0      # (at mean 100 a bf16 image has spread 0 or 1/2 ulp: rstd up to 1000)
+                if form == "f32" and shift == 100.0 and HW * (C // G) > 8:       # the unshifted E[x^2] - E[x]^2 in fp32: mean 100, spread 0.01
+                    assert _ratio(_groupnorm_emul(x, B, HW, G, w_, b_, 1e-6, sw, True, shifted=False), ref, bound) > 2.0
+                if form != "bf16, bf16 params" and HW * C >= 64 * 70 and (form == "f32" or shift < 100.0):            # bf16-rounded parameters where fp32 ones were given
+                    wrong = _groupnorm_emul(x, B, HW, G, _bf(wt), _bf(bs), 1e-6, sw, form == "f32")
+                    assert _ratio(wrong, ref, bound) > (2.0 if form == "f32" else 1.0), (form, sw, scale)
+    # a constant image: var = 0, the output is the bias
+    x = torch.full((B * HW, C), 3.25)
+    ref, bound = FB.groupnorm_bound(x, B, HW, G, wt, bs, 1e-6, False, out_fp32=True)
+    assert float((ref - bs.double()).abs().max()) == 0.0 and _ratio(_groupnorm_emul(x, B, HW, G, wt, bs, 1e-6, False, True), ref, bound) <= 1.0
+
+
+@pytest.mark.parametrize("K,xs", [(8, 0.1), (24, 1.0), (200, 1.0), (1152, 20.0)])
+def test_split_gemm_bound(K, xs):
+    g = torch.Generator().manual_seed(K)
+    x, w = torch.randn(65, K, generator=g) * xs, torch.randn(96, K, generator=g) * K ** -0.5
+    ref, bound = FB.split_gemm_bound(x, w)
+    xh, wh = x.to(BF), w.to(BF)
+    xl, wl = (x - xh.float()).to(BF), (w - wh.float()).to(BF)
+    a, b = torch.cat([xh, xl, xh], 1).float(), torch.cat([wh, wh, wl], 1).float()
+    assert _ratio(a.flip(-1) @ b.flip(-1).t(), ref, bound) <= 1.0
+    assert _ratio(xh.float() @ wh.float().t() + xh.float() @ wl.float().t(), ref, bound) > 1.0        # the lo.hi term missing (1.4 at K = 1152, 349 at K = 24)
+    assert _ratio(xh.float() @ wh.float().t(), ref, bound) > 2.0                                    # plain bf16 operands
+
+
+VQ_GRID = [(D, N) for D in (4, 32, 64, 256) for N in (1, 63, 64, 65, 1000, 16384)]              # scripts/fuzz_ops.py, 700 rows
+
+
+def _vq_case(D, N, seed, M=700):
+    g = torch.Generator().manual_seed(seed)
+    e, z = torch.randn(N, D, generator=g), torch.randn(M, D, generator=g)
+    if N > 8:
+        e[N // 2] = e[1]
+        z[0] = e[1]
+    return z, e
+
+
+@pytest.mark.parametrize("seed", [0, 1, 2])
+@pytest.mark.parametrize("D,N", VQ_GRID)
+def test_vq_margin_share_and_verdict(D, N, seed):
+    """From the reference alone: the rows the margin leaves to the fp32 arithmetic stay under VQ_EITHER_CAP (2 %) at every point of the fuzzer's
+    grid; torch's fp32 expression passes; an id one place off the fp64 arg-min on a decided row, an id out of range, and the later copy of a
+    duplicated entry fail."""
+    z, e = _vq_case(D, N, seed=seed)
+    want, either, allowed = FB.vq_margin(z, e)
+    share = float(either.double().mean())
+    print(f"vq_margin D={D} N={N} seed={seed}: EITHER share {share:.4f}")
+    assert share <= FB.VQ_EITHER_CAP
+    assert bool(allowed.gather(1, want[:, None]).all())
+    d = (z ** 2).sum(1, keepdim=True) + (e ** 2).sum(1) - 2 * z @ e.t()
+    bad, sh = FB.vq_verdict(torch.argmin(d, 1) + 7, z, e, offset=7)
+    assert bad == 0 and sh == share
+    if N > 8:
+        assert int(want[0]) == 1 and not bool(either[0])
+        dup = want.clone(); dup[0] = N // 2
+        assert FB.vq_verdict(dup, z, e)[0] == 1
+    if N > 1:
+        row = int((~either).float().argmax())                               # a decided row: only its fp64 arg-min is allowed
+        assert int(allowed[row].sum()) == 1
+        for step in (1, N - 1):                                             # one place off, either side
+            off = want.clone(); off[row] = (want[row] + step) % N
+            assert FB.vq_verdict(off, z, e)[0] == 1
+        assert int(((want + 1) % N != want).sum()) == 700 and FB.vq_verdict((want + 1) % N, z, e)[0] >= 700 * (1 - 2 * FB.VQ_EITHER_CAP)
+    oob = want.clone(); oob[-1] = 0x7fffffff
+    assert FB.vq_verdict(oob, z, e)[0] == 1
+
+
 # ------------------------------------------------------------------------------------------------------------------------ coverage pin
 LITERAL = re.compile(r"(?<![\w.])\d+(?:\.\d+)?e-\d+")
 
@@ -332,11 +574,35 @@ def test_fuzzers_hold_no_tolerance_literal():
         laws_src = f.read()
     assert not LITERAL.findall(laws_src) and "attn_bound_weighted" in laws_src and "torch.softmax" not in laws_src
     ops_src = _src("fuzz_ops.py")
+    assert set(LITERAL.findall(ops_src)) <= {"1e-5", "1e-6", "1e-12"}       # the whole file: the eps operands of the norms and of GroupNorm, nothing else
     norm = ops_src[ops_src.index('if kind in ("rmsnorm", "layernorm")'):ops_src.index('elif kind == "embedding"')]
     assert set(LITERAL.findall(norm)) <= {"1e-5", "1e-6", "1e-12"}          # the eps choices
     route = ops_src[ops_src.index('elif kind == "route"'):ops_src.index('elif kind == "vq_nearest"')]
     assert not LITERAL.findall(route) and route.count("run.judge(") == 2    # router and SwiGLU
-    for name in ("fuzz_gemm.py", "fuzz_attn.py", "fuzz_rope_epilogue.py", "fuzz_ops.py"):
+    for name in ("fuzz_gemm.py", "fuzz_attn.py", "fuzz_rope_epilogue.py", "fuzz_ops.py", "fuzz_seg.py"):
         s = _src(name)
         assert "from tests import fuzz_bounds as FB" in s and "run.judge(" in s and "{run}" in s, name
-        assert ".float() @" not in s.split("split_gemm")[0] and "torch.softmax" not in s, name      # no fp32 reference left in the changed branches
+        assert ".float() @" not in s and "torch.softmax" not in s, name      # no fp32 reference left in the changed branches
+
+
+def _branch(src, start, end):
+    return src[src.index(start):src.index(end)]
+
+
+def test_pixel_path_fuzzers_hold_no_tolerance_literal():
+    """scripts/fuzz_seg.py and the r06 branches of scripts/fuzz_ops.py: every floating-point kind goes through run.judge with a bound of
+    tests/fuzz_bounds.py (the quantiser through FB.vq_verdict and the cap), and no tolerance literal is left.  The one literal of fuzz_seg.py is
+    close64's relative 1e-6 between two fp64 evaluations of the eval loops' metrics - an equality kind, unchanged."""
+    seg = _src("fuzz_seg.py")
+    assert LITERAL.findall(seg) == ["1e-6"] and "rel=1e-6" in seg and "relerr" not in seg
+    assert "run.judge(" in seg and "guarded(" in seg and "intact(" in seg and "ops.copy_rows_batched(" in seg
+    for name in ("bilinear", "dense_pe", "mask_gate", "group_mean", "act", "softmax_rows", "sqnorm"):
+        assert f"FB.{name}_bound(" in seg, name
+    ops_src = _src("fuzz_ops.py")
+    vq = _branch(ops_src, 'elif kind == "vq_nearest"', 'elif kind == "split_gemm"')
+    assert "FB.vq_verdict(" in vq and "FB.VQ_EITHER_CAP" in vq and "topk" not in vq
+    sg = _branch(ops_src, 'elif kind == "split_gemm"', 'elif kind == "groupnorm_f32"')
+    assert "run.judge(" in sg and "FB.split_gemm_bound(" in sg
+    gn = ops_src[ops_src.index('elif kind == "groupnorm_f32"'):]
+    assert "run.judge(" in gn and "FB.groupnorm_bound(" in gn and "guarded(" in gn and "intact(" in gn
+    assert FB.VQ_EITHER_CAP == 0.02
